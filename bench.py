@@ -19,10 +19,16 @@ Beside it (``extra.replicas``) the same ranks also time query-sharded replicas
 the data path) and check that the sharded results equal the replica's, bit for
 bit.  ``--mode replicas`` makes the replicas the value.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ``--steps``
+steps and prints the headline (``value``, ``ms_per_step``, the config and the
+timed region's ``repairs``); ``--dump-outputs DIR`` also writes what the last
+timed step returned.  ``--full`` adds everything that takes runs of its own:
 ``roofline`` (the scan kernel's algorithmic code bytes / its HIP-event-timed
-duration against 8 TB/s) and ``cpu_baseline`` (the oracle's Faiss-1.7.1-order
-C restatement, OpenMP over queries, on a bounded sample of the same queries).
+duration against 8 TB/s, the measured HBM copy peak, the counter-file traffic),
+the same steps one batch at a time and the per-stage split, recall, the k = 100
+and host-path rates, with N > 1 the replicas beside the shards, and
+``cpu_baseline`` (the oracle's Faiss-1.7.1-order C restatement, OpenMP over
+queries, on a bounded sample of the same queries).
 """
 from __future__ import annotations
 
@@ -94,6 +100,14 @@ def parse():
                    help="shard flow: one communicator for every in-flight stream (default; the loop issues each "
                         "batch's all_to_all after the next batch's all_gather, so the communicator's stream never "
                         "holds a batch behind another's scan) or one per in-flight stream")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: HBM peak, roofline, the steps one batch at a time, stage split, k=100 "
+                        "and host-path rates, replicas (N > 1), recall and the CPU baseline (the --no-* options "
+                        "below drop single legs of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (distances and labels of its "
+                        "batch, as the caller of the timed path receives them) to DIR/D.npy (float32) and DIR/I.npy "
+                        "(float64; with N > 1 rank r writes D_rank<r>.npy / I_rank<r>.npy)")
     p.add_argument("--no-peak", action="store_true", help="skip the HBM stream-copy peak measurement")
     p.add_argument("--cpu-sample", type=int, default=10240, help="queries in the CPU-baseline sample")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline time budget (repetitions)")
@@ -114,7 +128,10 @@ def parse():
                         "has the depth A/Bs (plain: 0.109 / 0.123 / 0.110 ms with 2 / 3 / 4; shard flow at world "
                         "size 1: noisy, 0.14-0.20 ms with 3 and 0.17-0.19 with 2; one-GPU emulation at N = 2-8: "
                         "3 at or below 2)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -176,7 +193,6 @@ def main():
     ix.add(xb)
     log(f"added {ix.ntotal} vectors (lists [{lo},{hi})) in {time.time() - t0:.1f}s")
     ix.nprobe = args.nprobe
-    list_sizes = ix.invlists.list_sizes()
 
     xq_dev = torch.from_numpy(xq).to(dev).view(args.nbatches, Bg, args.d)
     k = args.k
@@ -200,11 +216,13 @@ def main():
     # algorithmic bytes: code_size x codes of every probed list in this
     # rank's range, per batch; the list-scan kernel covers all of them
     bytes_alg = []
-    for b in range(args.nbatches):
-        _, Iq = ix.coarse_device(xq_dev[b])
-        Iq = Iq.cpu().numpy()
-        sz = np.where(Iq >= 0, list_sizes[np.maximum(Iq, 0)], 0)  # lists outside [lo, hi) have size 0 here
-        bytes_alg.append(int(sz.sum()) * args.M)
+    if args.full:
+        list_sizes = ix.invlists.list_sizes()
+        for b in range(args.nbatches):
+            _, Iq = ix.coarse_device(xq_dev[b])
+            Iq = Iq.cpu().numpy()
+            sz = np.where(Iq >= 0, list_sizes[np.maximum(Iq, 0)], 0)  # lists outside [lo, hi) have size 0 here
+            bytes_alg.append(int(sz.sum()) * args.M)
     bytes_lists = bytes_alg
 
     merged = {}
@@ -265,7 +283,7 @@ def main():
     # the box's measured HBM peak (STREAM copy and a read sweep, 2 GiB each, best of 10),
     # beside the nominal 8 TB/s
     peak_measured = None
-    if not args.no_peak:
+    if args.full and not args.no_peak:
         try:
             import ctypes
 
@@ -311,6 +329,64 @@ def main():
     rs1 = ix.repair_stats()  # stale partial lists the merge repaired in the timed region: must be 0
     ix.set_timing(False)
     stages = ix.get_timing()
+    if args.dump_outputs:
+        # what the last timed step returned: its stream's output buffers, or, sharded,
+        # this rank's merged slice of the last batch (before any later pass reuses them)
+        if shard:
+            D_last, I_last = merged[(args.steps - 1) % args.nbatches]
+        else:
+            D_last, I_last = Dbufs[(args.steps - 1) % inflight], Ibufs[(args.steps - 1) % inflight]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(args.dump_outputs, f"D{sfx}.npy"), D_last.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, f"I{sfx}.npy"), I_last.cpu().numpy().astype(np.float64))
+
+    config_key = (f"nb{args.nb}-d{args.d}-IVF{args.nlist}-PQ{args.M}-np{args.nprobe}-k{k}-B{B}-w{world}-"
+                  f"{args.mode if world > 1 else ('shard-at-1' if shard else 'single')}"
+                  f"-c{args.centres}")
+
+    def headline(elapsed):
+        # the result line of a plain run; --full adds its keys to the same dict
+        return {
+            "metric": "queries/sec + recall@10, SIFT1M IVF-PQ (nlist=1024, M=16, nprobe=16)",
+            "value": args.steps * B * world / elapsed,  # all ranks together
+            "unit": "queries/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed * 1000.0 / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "full": args.full,
+            "data": f"synthetic (SIFT1M-shaped clustered integer-valued float32, {args.centres} centres, sigma 16, "
+                    "seeds base 1234 / train 4321 / queries 123); index trained on the GPU",
+            "config": {
+                "workload": f"IVF{args.nlist},PQ{args.M}x8 search, d={args.d}, nb={args.nb}, nprobe={args.nprobe}, "
+                            f"k={k}, batch={B} queries per GPU per step",
+                "parallelism": (f"list-range shards x{world} + RCCL all_gather / all_to_all ({args.comms} "
+                                f"communicator{'s' if args.comms == 'per-stream' else ''})" if shard
+                                else f"replicas x{world}" if world > 1 else "single GPU"),
+                "global_batch": B * world,
+                "inflight": inflight,
+                "key": config_key,
+            },
+            "repairs": rs1[1] - rs0[1],
+            "stale_reads": rs1[0] - rs0[0],
+        }
+
+    if not args.full:
+        if world > 1:
+            tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed = float(tt.item())
+        if rank == 0:
+            print(json.dumps(headline(elapsed)), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
     # the same steps one batch at a time on one stream (reported beside the value)
     serial_ms, stages_serial = None, None
     if inflight > 1:
@@ -415,8 +491,6 @@ def main():
         extra["shard_vs_replica_rows_identical"] = f"{int(ag[0].item())} / {int(ag[1].item())}"
         del ix_rep
 
-    queries = args.steps * B * world  # all ranks together
-    qps = queries / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps
     scan_ms, scan_n = stage_split["scan"]
     scan_avg_ms = scan_ms / max(scan_n, 1)
@@ -542,9 +616,6 @@ def main():
 
     traffic = None
     traffic_src = "no counter file"
-    config_key = (f"nb{args.nb}-d{args.d}-IVF{args.nlist}-PQ{args.M}-np{args.nprobe}-k{k}-B{B}-w{world}-"
-                  f"{args.mode if world > 1 else ('shard-at-1' if shard else 'single')}"
-                  f"-c{args.centres}")
     sha = lib_sha256()
     from faiss_amd import _lib
 
@@ -563,31 +634,9 @@ def main():
             traffic_src = f"unreadable counter file: {e}"
 
     if rank == 0:
-        out = {
-            "metric": "queries/sec + recall@10, SIFT1M IVF-PQ (nlist=1024, M=16, nprobe=16)",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+        out = headline(elapsed)
+        out.update({
             "ms_per_step_serial": serial_ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": f"synthetic (SIFT1M-shaped clustered integer-valued float32, {args.centres} centres, sigma 16, "
-                    "seeds base 1234 / train 4321 / queries 123); index trained on the GPU",
-            "config": {
-                "workload": f"IVF{args.nlist},PQ{args.M}x8 search, d={args.d}, nb={args.nb}, nprobe={args.nprobe}, "
-                            f"k={k}, batch={B} queries per GPU per step",
-                "parallelism": (f"list-range shards x{world} + RCCL all_gather / all_to_all ({args.comms} "
-                                f"communicator{'s' if args.comms == 'per-stream' else ''})" if shard
-                                else f"replicas x{world}" if world > 1 else "single GPU"),
-                "global_batch": B * world,
-                "inflight": inflight,
-                "key": config_key,
-            },
             "roofline": {
                 "bound": "hbm",
                 "achieved": achieved,
@@ -611,13 +660,11 @@ def main():
                 "end_to_end": {"alg_bytes": bytes_per_step, "ms_per_step": ms_per_step,
                                "achieved": bytes_per_step / (ms_per_step * 1e-3) / 1e9 if world == 1 else None},
             },
-            "repairs": rs1[1] - rs0[1],
-            "stale_reads": rs1[0] - rs0[0],
             "stages_ms_per_step": {s: v[0] / max(v[1], 1) for s, v in stage_split.items()},
             "recall": recall,
             "cpu_baseline": cpu_baseline,
             "extra": extra or None,
-        }
+        })
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -12,7 +12,7 @@ if [ "$SEL" != none ]; then
   timeout -k 10 600 python -u -m pytest "$R/tests" -m gpu -x -q --timeout 120 --timeout-method thread "${K[@]}" > "$O/tests.log" 2>&1
   rc=$?; tail -3 "$O/tests.log"; [ $rc -eq 0 ] || exit $rc
 fi
-B="--steps 30 --warmup 5 --no-cpu-baseline --no-recall --no-extra"
+B="--full --steps 30 --warmup 5 --no-cpu-baseline --no-recall --no-extra"
 for lib in default $(ls -d "$R"/chameleon-rag-acceleration_amd/lib/var/*/ 2>/dev/null); do
   name=$(basename "$lib")
   if [ "$lib" = default ]; then envs=""; else envs="IVFPQ_LIB=${lib}libivfpq.so"; fi

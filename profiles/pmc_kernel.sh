@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "${GRPS[@]}"; do
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex "$RX" --output-format csv -d "$OUT/g$i" -o run -- \
-    python3 $R/bench.py --no-recall --no-cpu-baseline --steps 6 --warmup 2 "$@" > "$OUT/g$i.json" 2> "$OUT/g$i.err" || exit $?
+    python3 $R/bench.py --full --no-recall --no-cpu-baseline --steps 6 --warmup 2 "$@" > "$OUT/g$i.json" 2> "$OUT/g$i.err" || exit $?
   i=$((i+1))
 done
 python3 $R/profiles/summarize_pmc.py "$OUT" | tee "$OUT/summary.txt"

@@ -14,7 +14,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_BRANCH SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM_RD SQ_IFETCH" \
            ${EXTRA_GROUP:+"$EXTRA_GROUP"}; do
   timeout -s KILL 90 rocprofv3 --pmc $grp --kernel-include-regex "$RX" --output-format csv -d "$OUT/g$i" -o run -- \
-    python3 $R/bench.py --no-recall --no-cpu-baseline --steps 4 --warmup 1 "$@" > "$OUT/g$i.log" 2>&1 || { echo "pass $i failed"; tail -3 "$OUT/g$i.log"; }
+    python3 $R/bench.py --full --no-recall --no-cpu-baseline --steps 4 --warmup 1 "$@" > "$OUT/g$i.log" 2>&1 || { echo "pass $i failed"; tail -3 "$OUT/g$i.log"; }
   i=$((i+1))
 done
 python3 - "$OUT" <<'PY'

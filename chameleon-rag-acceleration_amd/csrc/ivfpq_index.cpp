@@ -28,6 +28,7 @@
 #include "ivfpq_test.h"  // the test hooks are defined here too (not part of the drop-in header)
 #include "ivfpq_kernels.h"
 #include "ivfpq_build.h"
+#include "pq_flat.h"
 
 using namespace chivf;
 
@@ -1767,6 +1768,347 @@ int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n,
       HIPCHECK(hipMemcpyAsync(I + q0 * k, dI.p, sizeof(int64_t) * c * k, hipMemcpyDeviceToHost, s));
       HIPCHECK(hipStreamSynchronize(s));
     }
+  });
+}
+
+}  // extern "C"
+
+// ================================================================ flat PQ (IndexPQ)
+// faiss.IndexPQ: no coarse quantizer and no inverted lists -- one product quantizer
+// over the raw vectors, every code scanned for every query (pq_flat.hip).  The codes
+// live in one device image that grows geometrically; the label of a code is its
+// position.  Device calls on different streams are ordered one after the other
+// (one workspace per handle).
+struct ivfpq_pq_index {
+  int d = 0, M = 0, nbits = 8, ksub = 256, metric = IVFPQ_METRIC_L2, device = 0;
+  bool trained = false;
+  std::vector<float> codebook;  // [M][256][d / M]
+  int64_t ntotal = 0, cap = 0;  // codes in the image, rows allocated
+  DevBuf d_cb, d_codes;
+  DevBuf w_x, w_tab, w_pD, w_pI, w_D, w_I;  // staging, tables, partial lists
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;  // recorded after every device call, on done_stream
+  hipStream_t done_stream = nullptr;
+  bool done_pending = false;
+  std::mutex mu;
+
+  ~ivfpq_pq_index() {
+    if (done) (void)hipEventDestroy(done);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
+
+  void order_after(hipStream_t s) {
+    if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
+  }
+  void mark_done(hipStream_t s) {
+    HIPCHECK(hipEventRecord(done, s));
+    done_stream = s;
+    done_pending = true;
+  }
+  void quiesce() {
+    if (done_pending) HIPCHECK(hipEventSynchronize(done));
+    done_pending = false;
+  }
+
+  void upload_codebook() {
+    quiesce();
+    d_cb.ensure(sizeof(float) * codebook.size());
+    HIPCHECK(hipMemcpyAsync(d_cb.p, codebook.data(), sizeof(float) * codebook.size(), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    trained = true;
+  }
+
+  // room for n more codes: the image doubles (at least) when it is full
+  void reserve(int64_t n, hipStream_t s) {
+    require(ntotal + n < (int64_t)INT32_MAX, "IndexPQ holds at most 2^31 - 2 codes");
+    if (ntotal + n <= cap) return;
+    quiesce();
+    const int64_t ncap = std::max<int64_t>({ntotal + n, 2 * cap, 1024});
+    void* np = nullptr;
+    HIPCHECK(hipMalloc(&np, (size_t)ncap * M));
+    if (ntotal) {
+      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * M, hipMemcpyDeviceToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) {
+        (void)hipFree(np);
+        HIPCHECK(e);
+      }
+    }
+    d_codes.release();
+    d_codes.p = np;
+    d_codes.bytes = (size_t)ncap * M;
+    cap = ncap;
+  }
+
+  // encode n device-resident vectors behind the image; returns when they are in place
+  void add_dev(int64_t n, const float* xd, hipStream_t s) {
+    reserve(n, s);
+    order_after(s);
+    launch_pq_encode_flat(xd, n, d, d_cb.as<float>(), M, d_codes.as<uint8_t>() + ntotal * M, s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    ntotal += n;
+  }
+
+  void add_host(int64_t n, const float* x) {
+    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / (sizeof(float) * d)));
+    quiesce();
+    w_x.ensure(sizeof(float) * rows * d);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t c = std::min(rows, n - r0);
+      HIPCHECK(hipMemcpyAsync(w_x.p, x + r0 * d, sizeof(float) * c * d, hipMemcpyHostToDevice, stream));
+      add_dev(c, w_x.as<float>(), stream);
+    }
+  }
+
+  // queries per chunk: the tables (M KiB per query) within kChunkBytes, the grid's y extent
+  int64_t query_chunk(int64_t n) const {
+    return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
+  }
+
+  // c device-resident queries -> D, I (device), all on s
+  void search_chunk(const float* xd, int64_t c, int k, float* D, int64_t* I, hipStream_t s) {
+    if (ntotal == 0) {
+      launch_pq_fill_empty(D, I, c * k, ip(), s);
+      return;
+    }
+    w_tab.ensure(sizeof(float) * c * M * 256);
+    if (ip())
+      launch_ip_table(xd, c, d, d_cb.as<float>(), M, ksub, w_tab.as<float>(), s);
+    else
+      launch_l2_table(xd, c, d, d_cb.as<float>(), M, w_tab.as<float>(), s);
+    const PqScanPlan pl = pq_scan_plan(M, k, c, ntotal);
+    w_pD.ensure(sizeof(float) * pl.S * c * k);
+    w_pI.ensure(sizeof(int64_t) * pl.S * c * k);
+    launch_pq_scan(w_tab.as<float>(), c, d_codes.as<uint8_t>(), ntotal, M, k, ip(), pl, w_pD.as<float>(),
+                   w_pI.as<int64_t>(), s);
+    launch_merge_topk(pl.S, c, k, w_pD.as<float>(), w_pI.as<int64_t>(), D, I, s, ip());
+    HIPCHECK(hipGetLastError());
+  }
+
+  void search_dev(int64_t n, const float* xd, int k, float* D, int64_t* I, hipStream_t s) {
+    const int64_t qc = query_chunk(n);
+    order_after(s);
+    for (int64_t q0 = 0; q0 < n; q0 += qc) {
+      const int64_t c = std::min(qc, n - q0);
+      search_chunk(xd + q0 * d, c, k, D + q0 * k, I + q0 * k, s);
+    }
+    mark_done(s);
+  }
+
+  void search_host(int64_t n, const float* x, int k, float* D, int64_t* I) {
+    const int64_t qc = query_chunk(n);
+    quiesce();
+    w_x.ensure(sizeof(float) * qc * d);
+    w_D.ensure(sizeof(float) * qc * k);
+    w_I.ensure(sizeof(int64_t) * qc * k);
+    for (int64_t q0 = 0; q0 < n; q0 += qc) {
+      const int64_t c = std::min(qc, n - q0);
+      HIPCHECK(hipMemcpyAsync(w_x.p, x + q0 * d, sizeof(float) * c * d, hipMemcpyHostToDevice, stream));
+      search_chunk(w_x.as<float>(), c, k, w_D.as<float>(), w_I.as<int64_t>(), stream);
+      HIPCHECK(hipMemcpyAsync(D + q0 * k, w_D.p, sizeof(float) * c * k, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipMemcpyAsync(I + q0 * k, w_I.p, sizeof(int64_t) * c * k, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+    }
+  }
+};
+
+namespace {
+
+void check_pq(const ivfpq_pq_index* h) { require(h != nullptr, "null index handle"); }
+
+void check_search_args(const ivfpq_pq_index* h, int64_t n, const void* x, int k, const void* D, const void* I) {
+  require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+  require(h->trained, "index is not trained");
+  require(n >= 0, "negative query count");
+  require(n == 0 || (x && D && I), "null x / D / I");
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivfpq_pq_create(int d, int M, int nbits, int metric, int device, ivfpq_pq_index** out) {
+  return guarded([&] {
+    require(out != nullptr, "null output pointer");
+    require(d > 0 && M > 0, "d and M must be positive");
+    require(d % M == 0, "d must be a multiple of M");
+    require(nbits == 8, "only nbits=8 is supported");
+    require(pq_flat_supported_M(M),
+            "M=" + std::to_string(M) + " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)");
+    require(d <= 2048, "d > 2048 not supported");
+    require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    require(device >= 0 && device < ndev, "device ordinal out of range");
+    DeviceGuard g(device);
+    auto h = std::make_unique<ivfpq_pq_index>();
+    h->d = d;
+    h->M = M;
+    h->nbits = nbits;
+    h->metric = metric;
+    h->device = device;
+    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    *out = h.release();
+  });
+}
+
+int ivfpq_pq_free(ivfpq_pq_index* h) {
+  return guarded([&] {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->quiesce();
+    delete h;
+  });
+}
+
+int ivfpq_pq_train(ivfpq_pq_index* h, int64_t n, const float* x, int niter, uint64_t seed) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(x != nullptr && n > 0, "empty training set");
+    const int d = h->d, M = h->M, dsub = d / M;
+    // the IVF-PQ handle's GPU k-means (assignment on the GPU, double-precision mean on
+    // the host), run from a scratch handle that holds only its stream and workspaces
+    ivfpq_index km;
+    km.device = h->device;
+    km.init_stream();
+    std::vector<float> sub((size_t)n * dsub);
+    std::vector<float> cb((size_t)M * 256 * dsub);
+    for (int m = 0; m < M; m++) {
+      for (int64_t i = 0; i < n; i++) std::memcpy(&sub[(size_t)i * dsub], x + i * d + m * dsub, sizeof(float) * dsub);
+      km.kmeans(sub.data(), n, dsub, 256, niter, seed + 1 + (uint64_t)m, cb.data() + (size_t)m * 256 * dsub);
+    }
+    HIPCHECK(hipStreamSynchronize(km.stream));
+    h->codebook = std::move(cb);
+    h->upload_codebook();
+  });
+}
+
+int ivfpq_pq_set_trained(ivfpq_pq_index* h, const float* codebook) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(codebook != nullptr, "null codebook");
+    h->codebook.assign(codebook, codebook + (size_t)h->M * 256 * (h->d / h->M));
+    h->upload_codebook();
+  });
+}
+
+int ivfpq_pq_add(ivfpq_pq_index* h, int64_t n, const float* x) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(h->trained, "index is not trained");
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    h->add_host(n, x);
+  });
+}
+
+int ivfpq_pq_add_device(ivfpq_pq_index* h, int64_t n, const float* x, void* stream) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(h->trained, "index is not trained");
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    h->add_dev(n, x, (hipStream_t)stream);
+  });
+}
+
+int ivfpq_pq_add_codes(ivfpq_pq_index* h, int64_t n, const uint8_t* codes) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(h->trained, "index is not trained");
+    if (n <= 0) return;
+    require(codes != nullptr, "null codes");
+    h->reserve(n, h->stream);
+    h->quiesce();
+    HIPCHECK(hipMemcpyAsync(h->d_codes.as<uint8_t>() + h->ntotal * h->M, codes, (size_t)n * h->M,
+                            hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->ntotal += n;
+  });
+}
+
+int ivfpq_pq_reset(ivfpq_pq_index* h) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->quiesce();
+    h->d_codes.release();
+    h->ntotal = h->cap = 0;
+  });
+}
+
+int ivfpq_pq_search(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I) {
+  return guarded([&] {
+    check_pq(h);
+    check_search_args(h, n, x, k, D, I);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    if (n == 0) return;
+    h->search_host(n, x, k, D, I);
+  });
+}
+
+int ivfpq_pq_search_device(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I, void* stream) {
+  return guarded([&] {
+    check_pq(h);
+    check_search_args(h, n, x, k, D, I);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    if (n == 0) return;
+    h->search_dev(n, x, k, D, I, (hipStream_t)stream);
+  });
+}
+
+int64_t ivfpq_pq_ntotal(const ivfpq_pq_index* h) { return h ? h->ntotal : -1; }
+
+int ivfpq_pq_is_trained(const ivfpq_pq_index* h) { return h && h->trained ? 1 : 0; }
+
+int ivfpq_pq_get_dims(const ivfpq_pq_index* h, int* d, int* M, int* nbits, int* metric) {
+  return guarded([&] {
+    check_pq(h);
+    if (d) *d = h->d;
+    if (M) *M = h->M;
+    if (nbits) *nbits = h->nbits;
+    if (metric) *metric = h->metric;
+  });
+}
+
+int ivfpq_pq_get_codebook(const ivfpq_pq_index* h, float* out) {
+  return guarded([&] {
+    check_pq(h);
+    require(h->trained, "index is not trained");
+    require(out != nullptr, "null output pointer");
+    std::memcpy(out, h->codebook.data(), sizeof(float) * h->codebook.size());
+  });
+}
+
+int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out) {
+  return guarded([&] {
+    check_pq(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(i0 >= 0 && n >= 0 && i0 + n <= h->ntotal, "code range outside [0, ntotal)");
+    if (n == 0) return;
+    require(out != nullptr, "null output pointer");
+    h->quiesce();
+    HIPCHECK(hipMemcpyAsync(out, h->d_codes.as<uint8_t>() + i0 * h->M, (size_t)n * h->M, hipMemcpyDeviceToHost,
+                            h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
   });
 }
 

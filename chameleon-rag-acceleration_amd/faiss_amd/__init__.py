@@ -13,6 +13,7 @@ from .index import (  # noqa: F401
     IndexFlatIP,
     IndexFlatL2,
     IndexIVFPQ,
+    IndexPQ,
     ParameterSpace,
     downcast_index,
     extract_index_ivf,

@@ -92,6 +92,24 @@ SIGNATURES = {
     "ivfpq_load": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(c_handle)]),
     "ivfpq_flat_search": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int64,
                                          c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, c_i64p]),
+    # flat product quantizer (IndexPQ)
+    "ivfpq_pq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(c_handle)]),
+    "ivfpq_pq_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_pq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
+    "ivfpq_pq_set_trained": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_pq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
+    "ivfpq_pq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_pq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
+    "ivfpq_pq_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_pq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_pq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_pq_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_pq_is_trained": (ctypes.c_int, [c_handle]),
+    "ivfpq_pq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 4),
+    "ivfpq_pq_get_codebook": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_pq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
 }
 
 

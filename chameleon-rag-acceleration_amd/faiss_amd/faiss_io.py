@@ -28,6 +28,13 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
       LinearTransform): have_bias u8, A = u64 count + f32[d_out * d_in], b = u64 count + f32[count],
       d_in i32, d_out i32, is_trained u8
 
+    "IxPq"                                   IndexPQ (beir faiss_search.py:168-224)
+      index header
+      PQ:          d u64, M u64, nbits u64, centroids = u64 count + f32[count]   ([M][ksub][dsub])
+      codes = u64 count + u8[ntotal * code_size]
+      search_type i32 (0 = ST_PQ), encode_signs u8 (0), polysemous_ht i32 (0)
+    "IxPT" may wrap it in place of the IndexIVFPQ.
+
 Parity is unpinned: no Faiss-written file exists in the reference or this image
 (the reference's ``*.index`` files are not shipped), so the tests check a
 hand-assembled byte layout and round trips, not a file from real Faiss.
@@ -39,6 +46,7 @@ import struct
 import numpy as np
 
 FOURCC_IVFPQ = b"IwPQ"
+FOURCC_PQ = b"IxPq"
 FOURCC_FLAT = {0: b"IxFI", 1: b"IxF2"}  # metric_type: 0 = INNER_PRODUCT, 1 = L2
 HEADER_DUMMY = 1 << 20
 
@@ -49,7 +57,7 @@ FOURCC_LINEAR = b"LTra"
 
 def is_faiss_file(path) -> bool:
     with open(path, "rb") as f:
-        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM)
+        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ)
 
 
 class _Reader:
@@ -110,15 +118,63 @@ def parse_index(buf: bytes) -> dict:
         chain = [_parse_linear(r) for _ in range(nt)]
         if not chain or chain[0]["d_in"] != d:
             raise RuntimeError("pre-transform chain does not match the index dimension")
-        sub = _parse_ivfpq(r, r.fourcc())
+        sub = _parse_sub(r, r.fourcc())
         if sub["d"] != chain[-1]["d_out"]:
             raise RuntimeError("pre-transform output dimension does not match the wrapped index")
         z = {"kind": "pretransform", "d": d, "ntotal": ntotal, "metric": metric, "chain": chain, "index": sub}
     else:
-        z = _parse_ivfpq(r, h)
+        z = _parse_sub(r, h)
     if r.o != len(r.b):
         raise RuntimeError("trailing bytes after the index")
     return z
+
+
+def _parse_sub(r: "_Reader", h: bytes) -> dict:
+    return _parse_pq(r) if h == FOURCC_PQ else _parse_ivfpq(r, h)
+
+
+def _parse_pq(r: "_Reader") -> dict:
+    """IndexPQ after its fourcc -> {kind "pq", d, ntotal, M, nbits, metric, is_trained,
+    codebook [M][ksub][dsub], codes u8 [ntotal][code_size]}."""
+    d, ntotal, is_trained, metric = r.header()
+    pd = r.fmt("Q")
+    M = r.fmt("Q")
+    nbits = r.fmt("Q")
+    cb = r.vector(np.float32)
+    codes = r.vector(np.uint8)
+    search_type = r.fmt("i")
+    r.fmt("B")  # encode_signs
+    r.fmt("i")  # polysemous_ht
+    if pd != d or nbits != 8 or M == 0 or d % M or (is_trained and cb.size != M * 256 * (d // M)):
+        raise RuntimeError("unsupported PQ shape (8-bit codes)")
+    if search_type != 0:
+        raise RuntimeError("only IndexPQ search_type ST_PQ is supported")
+    if codes.size != ntotal * M:
+        raise RuntimeError("IndexPQ codes do not match ntotal")
+    return {"kind": "pq", "d": d, "ntotal": ntotal, "M": M, "nbits": nbits, "metric": metric,
+            "is_trained": is_trained, "codebook": cb.reshape(M, 256, d // M) if cb.size else cb,
+            "codes": codes.reshape(ntotal, M)}
+
+
+def parse_pq(buf: bytes) -> dict:
+    """Faiss IndexPQ ("IxPq") bytes -> _parse_pq's dict."""
+    r = _Reader(buf)
+    if r.fourcc() != FOURCC_PQ:
+        raise RuntimeError("not a Faiss IndexPQ file")
+    z = _parse_pq(r)
+    if r.o != len(r.b):
+        raise RuntimeError("trailing bytes after the index")
+    return z
+
+
+def serialize_pq(d, M, nbits, metric, codebook, codes, is_trained=True) -> bytes:
+    """The inverse of parse_pq: codes uint8 [ntotal][M]."""
+    codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    code_size = M * nbits // 8
+    return b"".join([FOURCC_PQ, _header(d, codes.size // code_size, is_trained, metric),
+                     struct.pack("<QQQ", d, M, nbits),
+                     _vector(np.ascontiguousarray(codebook, np.float32).reshape(-1)), _vector(codes),
+                     struct.pack("<iBi", 0, 0, 0)])
 
 
 def _parse_linear(r: _Reader) -> dict:

@@ -12,6 +12,8 @@ The surface mirrors what Chameleon's callers use on ``faiss`` (SURVEY.md
   ``beir/beir/retrieval/search/dense/faiss_index.py:13-96``;
   ``ralm/retriever/faiss_retriever.py:18-275``;
   ``my_faiss_extract_scripts/extract_FPGA_required_data.py:174-248``);
+* ``IndexPQ(d, M, nbits, metric)`` (beir ``faiss_search.py:168-224``
+  PQFaissSearch, plain or behind ``IndexPreTransform(OPQMatrix, ...)``);
 * ``IndexFlatL2`` (the coarse quantizer; exact search on the GPU);
 * ``index_factory``, ``ParameterSpace``, ``read_index / write_index``,
   ``swig_ptr``, ``vector_to_array``, ``get_num_gpus``.
@@ -647,6 +649,147 @@ class IndexIVFPQ:
         return Dq, Iq, tok.value
 
 
+class IndexPQ:
+    """faiss.IndexPQ: one product quantizer over the raw vectors, every code
+    scanned for every query (beir faiss_search.py:168-224, nbits_experiments_fix_m.py:89).
+    Labels are positions: there is no id map, as in Faiss."""
+
+    polysemous_ht = 0
+
+    def __init__(self, d, M, nbits=8, metric=METRIC_L2, device=None):
+        self.d = int(d)
+        self.M = int(M)
+        self.nbits = int(nbits)
+        self.metric_type = metric
+        self.device = _default_device() if device is None else int(device)
+        self.verbose = False
+        self.niter_pq = 25
+        self.seed = 1234
+        h = _lib.c_handle()
+        _lib.check(_lib.load().ivfpq_pq_create(self.d, self.M, self.nbits, metric, self.device, ctypes.byref(h)))
+        self._h = h
+        self.pq = _ProductQuantizer(self)
+        self._codebook_cache = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ivfpq_pq_free(h)
+            self._h = None
+
+    @property
+    def ntotal(self):
+        return int(_lib.load().ivfpq_pq_ntotal(self._h))
+
+    @property
+    def is_trained(self):
+        return bool(_lib.load().ivfpq_pq_is_trained(self._h))
+
+    @property
+    def code_size(self):
+        return self.M
+
+    def codebook(self):
+        if self._codebook_cache is None:
+            cb = np.empty((self.M, 1 << self.nbits, self.d // self.M), np.float32)
+            _lib.check(_lib.load().ivfpq_pq_get_codebook(self._h, _ptr(cb, _lib.c_f32p)))
+            self._codebook_cache = cb
+        return self._codebook_cache
+
+    def _codes(self, i0, n):
+        out = np.empty((n, self.M), np.uint8)
+        _lib.check(_lib.load().ivfpq_pq_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
+        return out
+
+    @property
+    def codes(self):
+        """uint8 [ntotal * M] (faiss.vector_to_array(index.codes))."""
+        return self._codes(0, self.ntotal).reshape(-1)
+
+    # ----------------------------------------------------------- build path
+    def train(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_pq_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_pq, self.seed))
+        self._codebook_cache = None
+
+    def set_trained(self, codebook):
+        """Install a trained codebook [M][256][d/M]."""
+        cb = np.ascontiguousarray(codebook, np.float32).reshape(-1)
+        if cb.size != self.M * (1 << self.nbits) * (self.d // self.M):
+            raise RuntimeError("codebook has the wrong size")
+        _lib.check(_lib.load().ivfpq_pq_set_trained(self._h, _ptr(cb, _lib.c_f32p)))
+        self._codebook_cache = None
+
+    def add(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_pq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
+
+    def add_codes(self, codes):
+        """Append precomputed codes uint8 [n][M]."""
+        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.M)
+        _lib.check(_lib.load().ivfpq_pq_add_codes(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p)))
+
+    def reset(self):
+        _lib.check(_lib.load().ivfpq_pq_reset(self._h))
+
+    def reconstruct_n(self, i0, n):
+        """Decoded on the host from the codebook and the codes."""
+        return decode_pq(self.codebook(), self._codes(i0, n))
+
+    def reconstruct(self, i):
+        return self.reconstruct_n(i, 1)[0]
+
+    # ------------------------------------------------------------ search path
+    _check_k = IndexIVFPQ._check_k
+    _check_dev = IndexIVFPQ._check_dev
+    _dev_outputs = IndexIVFPQ._dev_outputs
+    _stream = IndexIVFPQ._stream
+
+    def search(self, x, k):
+        x = _f32(x, self.d)
+        self._check_k(k)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _lib.check(_lib.load().ivfpq_pq_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
+                                               _ptr(I, _lib.c_i64p)))
+        return D, I
+
+    def search_device(self, x, k, D=None, I=None, stream=None):
+        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
+        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
+        import torch
+
+        self._check_k(k)
+        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
+        D, I = self._dev_outputs(x, k, D, I)
+        _lib.check(_lib.load().ivfpq_pq_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
+                                                      I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+    def add_device(self, x, stream=None):
+        """add with the vectors already in HBM; returns once the codes are in place."""
+        import torch
+
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.float32, (n, self.d))
+        _lib.check(_lib.load().ivfpq_pq_add_device(self._h, n, x.data_ptr(),
+                                                   ctypes.c_void_p(self._stream(x, stream))))
+
+
+def decode_pq(codebook, codes):
+    """ProductQuantizer::decode: codebook [M][256][dsub], codes uint8 [n][M] -> float32 [n][M * dsub]."""
+    M, _, dsub = codebook.shape
+    codes = np.asarray(codes, np.uint8).reshape(-1, M)
+    out = np.empty((codes.shape[0], M * dsub), np.float32)
+    for m in range(M):
+        out[:, m * dsub:(m + 1) * dsub] = codebook[m][codes[:, m]]
+    return out
+
+
 def merge_topk_device(Ds, Is, metric=METRIC_L2, stream=None):
     """Merge S sorted partial results (torch [S, n, k]) into [n, k] on the GPU:
     ascending L2 distances, or descending inner products (metric)."""
@@ -668,6 +811,7 @@ def merge_topk_device(Ds, Is, metric=METRIC_L2, stream=None):
 
 # ------------------------------------------------------------------ factory / IO
 
+_PQ_FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?PQ(\d+)(?:x(\d+))?$")
 _FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x(\d+))?$")
 
 
@@ -685,11 +829,30 @@ def parse_factory(key):
     return base + (int(m.group(1)), int(m.group(2)) if m.group(2) else -1)
 
 
+def parse_pq_factory(key):
+    """'[OPQ<M>[_<dout>],]PQ<M>[x8]' -> (M, nbits) or (M, nbits, opq_M, opq_dout)
+    (opq_dout = -1: d); None for any other key."""
+    m = _PQ_FACTORY_RE.match(key.replace(" ", ""))
+    if not m:
+        return None
+    base = (int(m.group(3)), int(m.group(4)) if m.group(4) else 8)
+    if m.group(1) is None:
+        return base
+    return base + (int(m.group(1)), int(m.group(2)) if m.group(2) else -1)
+
+
 def index_factory(d, key, metric=METRIC_L2, device=None):
-    """faiss.index_factory(d, "IVF1024,PQ16") (bench_polysemous_1bn.py:272) and the
-    OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17)."""
+    """faiss.index_factory(d, "IVF1024,PQ16") (bench_polysemous_1bn.py:272), the
+    OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), and the flat
+    "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224)."""
     from .transform import IndexPreTransform, OPQMatrix
 
+    f = parse_pq_factory(key)
+    if f is not None:
+        if len(f) == 2:
+            return IndexPQ(d, f[0], f[1], metric, device)
+        opq = OPQMatrix(d, f[2], f[3])
+        return IndexPreTransform(opq, IndexPQ(opq.d_out, f[0], f[1], metric, device))
     f = parse_factory(key)
     if len(f) == 3:
         nlist, M, nbits = f
@@ -725,18 +888,33 @@ def _ivfpq_bytes(index):
                                     index.centroids(), index.codebook(), lists)
 
 
+def _pq_bytes(index):
+    if not index.is_trained:
+        raise RuntimeError("IndexPQ is written once trained")
+    return faiss_io.serialize_pq(index.d, index.M, index.nbits, index.metric_type, index.codebook(),
+                                 index._codes(0, index.ntotal))
+
+
+def _sub_bytes(index):
+    return _pq_bytes(index) if isinstance(index, IndexPQ) else _ivfpq_bytes(index)
+
+
 def write_index(index, path, fmt="faiss"):
-    """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPreTransform
-    binary layout (``faiss.read_index`` loads it; faiss_io.py); "native": this
-    library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
+    """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
+    IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
+    "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform
 
     if isinstance(index, IndexPreTransform):
         if fmt != "faiss" or not index.is_trained:
             raise RuntimeError("IndexPreTransform is written in the Faiss layout once trained")
         chain = [(t.A, t.b, t.d_in, t.d_out, t.is_trained) for t in index.chain]
-        buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, _ivfpq_bytes(index.index),
+        buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, _sub_bytes(index.index),
                                               index.ntotal)
+    elif isinstance(index, IndexPQ):
+        if fmt != "faiss":
+            raise RuntimeError("IndexPQ is written in the Faiss layout")
+        buf = _pq_bytes(index)
     elif fmt == "native" or not index.is_trained:
         _lib.check(_lib.load().ivfpq_save(index._h, str(path).encode()))
         return
@@ -761,18 +939,31 @@ def _ivfpq_from_dict(z, device):
     return idx
 
 
+def _pq_from_dict(z, device):
+    idx = IndexPQ(z["d"], z["M"], z["nbits"], z["metric"], device)
+    if z["is_trained"]:
+        idx.set_trained(z["codebook"])
+        if z["ntotal"]:
+            idx.add_codes(z["codes"])
+    return idx
+
+
+def _index_from_dict(z, device):
+    return _pq_from_dict(z, device) if z["kind"] == "pq" else _ivfpq_from_dict(z, device)
+
+
 def read_index(path, device=None):
-    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPreTransform ("IxPT") file or a
-    CHIVFPQ1 image onto ``device``."""
+    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexPreTransform ("IxPT")
+    file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
     if faiss_io.is_faiss_file(path):
         with open(path, "rb") as f:
             z = faiss_io.parse_index(f.read())
         if z["kind"] != "pretransform":
-            return _ivfpq_from_dict(z, device)
+            return _index_from_dict(z, device)
         from .transform import IndexPreTransform, _linear_from_dict
 
-        return IndexPreTransform([_linear_from_dict(t) for t in z["chain"]], _ivfpq_from_dict(z["index"], device))
+        return IndexPreTransform([_linear_from_dict(t) for t in z["chain"]], _index_from_dict(z["index"], device))
     h = _lib.c_handle()
     L = _lib.load()
     _lib.check(L.ivfpq_load(str(path).encode(), device, ctypes.byref(h)))

@@ -228,11 +228,12 @@ class IndexPreTransform:
 
     @property
     def nprobe(self):
-        return self.index.nprobe
+        return getattr(self.index, "nprobe", 1)  # an IndexPQ has no lists to probe
 
     @nprobe.setter
     def nprobe(self, p):
-        self.index.nprobe = p
+        if hasattr(self.index, "nprobe"):
+            self.index.nprobe = p
 
     @property
     def device(self):

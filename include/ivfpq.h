@@ -232,6 +232,43 @@ int ivfpq_load(const char* path, int device, ivfpq_index** out);
 int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n, const float* x, int k, int metric,
                       float* D, int64_t* I);
 
+/* ---- flat product quantizer: faiss.IndexPQ(d, M, nbits, metric) -------------------
+ * (beir faiss_search.py:168-224 PQFaissSearch, also behind IndexPreTransform(OPQMatrix);
+ * my_faiss_extract_scripts/nbits_experiments_fix_m.py:89).  No coarse quantizer and no
+ * id map: every code is scanned for every query and the label of a code is its
+ * position.  Tables as pq.compute_distance_tables (L2: |q_m - C_mj|^2) /
+ * compute_inner_prod_tables, sums as pq_knn_search_with_tables (from 0, ascending m).
+ * nbits must be 8; M in {8, 16, 32, 48, 64, 80, 96, 112, 128}; d <= 2048; k <= 1024.
+ * Same conventions, errors and locking as above (one mutex per handle); device calls
+ * of one handle on different streams run one after the other. */
+typedef struct ivfpq_pq_index ivfpq_pq_index;
+
+int ivfpq_pq_create(int d, int M, int nbits, int metric, int device, ivfpq_pq_index** out);
+int ivfpq_pq_free(ivfpq_pq_index* h);
+/* Index.train(x): sub-space m by the GPU k-means on the raw sub-vectors, seed + 1 + m. */
+int ivfpq_pq_train(ivfpq_pq_index* h, int64_t n, const float* x, int niter, uint64_t seed);
+/* Install a trained codebook [M][256][d/M] (pq.centroids). */
+int ivfpq_pq_set_trained(ivfpq_pq_index* h, const float* codebook);
+/* Index.add(x) (beir faiss_index.py FaissTrainIndex.build: chunks of 50 000): encoded on
+ * the GPU and appended to the device code image, which grows geometrically. */
+int ivfpq_pq_add(ivfpq_pq_index* h, int64_t n, const float* x);
+/* The same with x in HBM, on `stream` (hipStream_t, NULL = default); returns when the codes are in place. */
+int ivfpq_pq_add_device(ivfpq_pq_index* h, int64_t n, const float* x, void* stream);
+/* Append precomputed codes uint8 [n][M] (e.g. from a loaded index file). */
+int ivfpq_pq_add_codes(ivfpq_pq_index* h, int64_t n, const uint8_t* codes);
+/* Index.reset(): drop the codes, keep the codebook. */
+int ivfpq_pq_reset(ivfpq_pq_index* h);
+/* Index.search(x, k) (beir faiss_index.py:22, k = 1000).  Queries are taken in chunks so
+ * that the table workspace stays bounded. */
+int ivfpq_pq_search(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I);
+int ivfpq_pq_search_device(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I, void* stream);
+int64_t ivfpq_pq_ntotal(const ivfpq_pq_index* h);
+int ivfpq_pq_is_trained(const ivfpq_pq_index* h);
+int ivfpq_pq_get_dims(const ivfpq_pq_index* h, int* d, int* M, int* nbits, int* metric);
+int ivfpq_pq_get_codebook(const ivfpq_pq_index* h, float* out); /* [M][256][d/M] */
+/* codes [i0, i0 + n) of the image, uint8 [n][M] (IndexPQ.codes) */
+int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

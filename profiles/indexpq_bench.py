@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""IndexPQ throughput on one MI355X, and the paired comparison with the only stand-in
+the IVF engine offers (an inner-product IndexIVFPQ over zero-centroid pseudo-lists,
+every list probed).
+
+    python profiles/indexpq_bench.py [--out profiles/indexpq_bench.json] [--nb 1000000]
+
+Every GPU step runs in a child process of its own under ``timeout``; the first step that
+fails ends the run (nothing else is started on the GPU) and no JSON is written.  Times
+are device events around whole ``search_device`` calls (table build + scan + merge) after
+a warm-up, over a window of at least a second.  Code bytes and LDS gathers are counted
+from the shapes: the scan makes ceil(nq / G) passes over nb * M code bytes and nq * nb * M
+table look-ups.  Registers, LDS and workgroups per CU are the compiler's resource report
+for the kernel instance each shape runs ("IndexPQ").
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "chameleon-rag-acceleration_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+# k_pq_scan<G, R, MB> as compiled for gfx950 (-Rpass-analysis=kernel-resource-usage): VGPRs
+# (+ AGPRs), LDS KiB, and the 4-wave workgroups per CU that the two allow (160 KiB of LDS,
+# 512 registers per lane and SIMD)
+KERNELS = {
+    "k_pq_scan<4,1,8>": {"vgprs": 176, "agprs": 0, "lds_kib": 32, "workgroups_per_cu": 2},
+    "k_pq_scan<4,1,16>": {"vgprs": 218, "agprs": 0, "lds_kib": 64, "workgroups_per_cu": 2},
+    "k_pq_scan<4,4,8>": {"vgprs": 221, "agprs": 0, "lds_kib": 72, "workgroups_per_cu": 2},
+    "k_pq_scan<4,4,16>": {"vgprs": 233, "agprs": 0, "lds_kib": 104, "workgroups_per_cu": 1},
+    "k_pq_scan<4,16,8>": {"vgprs": 256, "agprs": 13, "lds_kib": 72, "workgroups_per_cu": 1},
+    "k_pq_scan<4,16,16>": {"vgprs": 256, "agprs": 34, "lds_kib": 104, "workgroups_per_cu": 1},
+}
+LDS_PEAK_BYTES_PER_S = 256 * 256 * 2.4e9  # 256 B/clk/CU (ds_read_b128) x 256 CUs x 2.4 GHz
+
+SHAPES = {
+    "sift_like": dict(d=128, M=16, metric="l2", nq=1024, k=10),
+    "beir_like_k10": dict(d=768, M=96, metric="ip", nq=1024, k=10),
+    "beir_like_k1000": dict(d=768, M=96, metric="ip", nq=1024, k=1000),
+}
+STEP_TIMEOUT = 420
+
+
+def scan_kernel(M, k):
+    G, R = 4, (1 if k <= 64 else 4 if k <= 256 else 16)
+    return f"k_pq_scan<{G},{R},{8 if M == 8 else 16}>", G
+
+
+def timed(fn, torch, min_seconds=1.0):
+    """ms per call: two warm-up calls, then a window of at least min_seconds."""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    one = max(a.elapsed_time(b), 1e-3)
+    reps = int(min(200, max(3, min_seconds * 1000.0 / one)))
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps, reps
+
+
+def random_index(faiss, np, d, M, metric, nb, seed):
+    rng = np.random.default_rng(seed)
+    ix = faiss.IndexPQ(d, M, 8, faiss.METRIC_L2 if metric == "l2" else faiss.METRIC_INNER_PRODUCT)
+    cb = rng.standard_normal((M, 256, d // M), dtype=np.float32)
+    ix.set_trained(cb)
+    codes = rng.integers(0, 256, (nb, M), dtype=np.uint8)
+    ix.add_codes(codes)
+    return ix, cb, codes
+
+
+def step_shape(name, nb):
+    import numpy as np
+    import torch
+
+    import faiss_amd as faiss
+
+    s = SHAPES[name]
+    ix, _, _ = random_index(faiss, np, s["d"], s["M"], s["metric"], nb, 1)
+    xq = torch.from_numpy(np.random.default_rng(2).standard_normal((s["nq"], s["d"]), dtype=np.float32)).cuda()
+    D = torch.empty((s["nq"], s["k"]), dtype=torch.float32, device="cuda")
+    I = torch.empty((s["nq"], s["k"]), dtype=torch.int64, device="cuda")
+    ms, reps = timed(lambda: ix.search_device(xq, s["k"], D, I), torch)
+    assert int(I.min()) >= 0 and int(I.max()) < nb
+    kern, G = scan_kernel(s["M"], s["k"])
+    gathers = s["nq"] * nb * s["M"]
+    out = dict(s, nb=nb, ms_per_batch=ms, batches_timed=reps, queries_per_s=s["nq"] / ms * 1e3, kernel=kern,
+               **KERNELS[kern], queries_per_workgroup=G,
+               code_bytes_read=-(-s["nq"] // G) * nb * s["M"], lds_gathers=gathers,
+               lds_gathers_per_s=gathers / ms * 1e3,
+               lds_read_ceiling_fraction=gathers * 4 / (ms * 1e-3) / LDS_PEAK_BYTES_PER_S)
+    return out
+
+
+def step_pair(nb):
+    """IndexPQ against the IVF stand-in on the same codes, three alternating runs each."""
+    import numpy as np
+    import torch
+
+    import faiss_amd as faiss
+
+    d, M, nq, k, nlist = 512, 64, 1024, 10, 64
+    pq, cb, codes = random_index(faiss, np, d, M, "ip", nb, 3)
+    ivf = faiss.IndexIVFPQ(None, d, nlist, M, 8, faiss.METRIC_INNER_PRODUCT)
+    ivf.set_trained(np.zeros((nlist, d), np.float32), cb)
+    ivf.add_preencoded(np.arange(nb, dtype=np.int64) % nlist, codes, np.arange(nb, dtype=np.int64))
+    ivf.nprobe = nlist
+    xq = torch.from_numpy(np.random.default_rng(4).standard_normal((nq, d), dtype=np.float32)).cuda()
+    Iq = torch.arange(nlist, dtype=torch.int64, device="cuda").repeat(nq, 1).contiguous()
+    Dp, Ip = pq.search_device(xq, k)
+    Dv, Iv = ivf.search_preassigned_device(xq, k, Iq)
+    torch.cuda.synchronize()
+    same = bool((Ip == Iv).all()) and bool((Dp == Dv).all())
+    runs = []
+    for _ in range(3):
+        t_ivf, _ = timed(lambda: ivf.search_preassigned_device(xq, k, Iq), torch)
+        t_pq, _ = timed(lambda: pq.search_device(xq, k), torch)
+        runs.append({"ivf_stand_in_ms": t_ivf, "indexpq_ms": t_pq, "ratio": t_ivf / t_pq})
+    return dict(d=d, M=M, metric="ip", nb=nb, nq=nq, k=k, pseudo_lists=nlist, results_identical=same, runs=runs,
+                indexpq_no_slower_in_every_run=all(r["indexpq_ms"] <= r["ivf_stand_in_ms"] for r in runs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "indexpq_bench.json"))
+    ap.add_argument("--nb", type=int, default=1_000_000)
+    ap.add_argument("--step")
+    a = ap.parse_args()
+    if a.step:  # child: one GPU step, one JSON line
+        r = step_pair(a.nb) if a.step == "pair" else step_shape(a.step, a.nb)
+        print("RESULT " + json.dumps(r), flush=True)
+        return 0
+    result = {"nb": a.nb, "shapes": {}, "lds_peak_bytes_per_s": LDS_PEAK_BYTES_PER_S}
+    for step in list(SHAPES) + ["pair"]:
+        cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT), sys.executable, os.path.abspath(__file__), "--step", step,
+               "--nb", str(a.nb)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not lines:
+            sys.stderr.write(p.stdout[-4000:])
+            sys.stderr.write(f"\nstep {step} failed (exit {p.returncode}); stopping\n")
+            return 1
+        r = json.loads(lines[-1][7:])
+        print(step, json.dumps(r), flush=True)
+        if step == "pair":
+            result["pair_vs_ivf_stand_in"] = r
+        else:
+            result["shapes"][step] = r
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -164,8 +164,6 @@ constexpr int kSegmentedNlist = 8192;
 // on, device searches on different streams overlap, each on its own per-stream
 // workspace; off, a search is ordered after every search still in flight on
 // another stream.  IVFPQ_INFLIGHT=1 in the environment turns it on for new handles.
-constexpr int kInflightFreeCus = 16;
-
 bool inflight_default() {
   const char* e = std::getenv("IVFPQ_INFLIGHT");
   return e && e[0] == '1';
@@ -296,11 +294,6 @@ struct ivfpq_index {
     ListPlan pl;
     pl.cap = (int)nq;
     pl.max_items = list_scan_max_items(nq * np, nloc, G);
-    // leave_free (a full search with batches in flight): the scan leaves kInflightFreeCus
-    // CUs to the other streams' coarse and merge kernels (r06x sweep: C2 step -2.5 %;
-    // DESIGN.md section 4); one batch at a time, and in the shard flow's preassigned
-    // searches, where the sweep was inconclusive, it takes them all
-    pl.grid = scan_lists_grid(M, k, leave_free ? kInflightFreeCus : 0);
     if (!w.p_cnt.p || w.p_cnt.bytes < sizeof(int32_t) * 2 * nloc) {
       // kept zero between batches by k_scan_lists; zeroed once here
       w.p_cnt.ensure(sizeof(int32_t) * 2 * nloc);
@@ -361,6 +354,12 @@ struct ivfpq_index {
     pl.qmask = w.p_qmask.as<uint64_t>();
     pl.order = d_order.p ? d_order.as<int32_t>() : nullptr;
     pl.fused = scan_fused_plan(nloc, pl.max_items, M) ? 1 : 0;
+    // leave_free (a full search with batches in flight): the scan leaves
+    // scan_inflight_free_cus() CUs, chosen per scan kernel, to the other streams' coarse
+    // and merge kernels (r06x sweep of the one-pass scans: C2 step -2.5 %;
+    // DESIGN.md section 4); one batch at a time, and in the shard flow's preassigned
+    // searches, where the sweep was inconclusive, it takes them all
+    pl.grid = scan_lists_grid(M, k, pl.fused != 0, leave_free ? scan_inflight_free_cus(M, k, pl.fused != 0) : 0);
     return pl;
   }
 

@@ -166,7 +166,10 @@ bool scan_fused_plan(int nloc, int max_items, int M);
 
 int list_scan_group(int M, int k);  // pairs per work item (G) used for (M, k)
 int list_scan_max_items(int64_t npairs, int nloc, int G);
-int scan_lists_grid(int M, int k, int free_cus = 0);  // persistent grid (2-3 workgroups per CU by LDS) on all but free_cus CUs
+// persistent grid on all but free_cus CUs: the workgroups per CU resident of the kernel
+// that launch_scan_lists picks for (M, k, fused = ListPlan::fused)
+int scan_lists_grid(int M, int k, bool fused, int free_cus = 0);
+int scan_inflight_free_cus(int M, int k, bool fused);  // free_cus of a search with batches in flight
 bool scan_supported_M(int M);
 // list scan + probe merge; ev_lists (nullable): two events recorded around the list-scan kernel alone
 void launch_scan_lists(const ScanArgs& a, const ListPlan& plan, hipStream_t s, hipEvent_t* ev_lists = nullptr);

@@ -2560,7 +2560,23 @@ constexpr bool kScanPrefetch = SCAN_PREFETCH != 0;  // (-DSCAN_PREFETCH=0: table
 #ifndef SCAN_LEAN_JB
 #define SCAN_LEAN_JB 6
 #endif
-constexpr int kLeanJB = SCAN_LEAN_JB;  // code chunks per super-batch of k_scan_lean
+#ifndef SCAN_LEAN_SPLIT
+#define SCAN_LEAN_SPLIT 1
+#endif
+#ifndef SCAN_LEAN_SPLIT_JB
+#define SCAN_LEAN_SPLIT_JB 6
+#endif
+// (-DSCAN_LEAN_SPLIT=0: the one-pass k_scan_lean, whole LUT in LDS, two workgroups per CU)
+// The two-pass form is for M = 16 only.  The one-pass M = 8 kernel is already resident
+// three per CU (158 VGPRs, 38,976 B), so the split cannot raise its residency and only
+// adds two barriers per super-batch: it measured 85.5 vs 84.6 us (profiles/scan_split_lut.md).
+constexpr bool lean_split(int M) { return SCAN_LEAN_SPLIT != 0 && M == 16; }
+// code chunks per super-batch of k_scan_lean
+constexpr int lean_jb(int M) { return lean_split(M) ? SCAN_LEAN_SPLIT_JB : SCAN_LEAN_JB; }
+// CUs the persistent scan leaves to the other streams while batches are in flight
+// (one-pass scans: r06x sweep, C2 step -2.5 % with 16; two-pass scan: the sweeps of
+// profiles/scan_split_lut.md, see scan_inflight_free_cus)
+constexpr int kInflightFreeCus = 16, kInflightFreeCusSplit = 96;
 
 // ------------------------------------------------ lean list scan (k <= 16)
 // k_scan_lean: the C2 configuration (G = 4 pairs per item, k <= 16, M <= 16,
@@ -2588,13 +2604,34 @@ __device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v) {  // lane i <- lan
   return ((uint64_t)hi << 32) | lo;
 }
 
-template <int M, int JB>
-__global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
+// k_scan_lean, SPLIT (the default): the LUT is built and gathered in two halves by
+// sub-quantizer through one [M / 2][256] buffer.  A key is the sequential sum
+// dis0 + L[0] + ... + L[M - 1], so the entries of m < M / 2 and of m >= M / 2 are
+// never needed together once each code's partial sum waits in a register: per
+// super-batch low rows -> LDS, gather, high rows -> the same LDS, gather.  Items,
+// codes, table rows and the order of every addition are those of the one-pass
+// form (bit-identical results); the LDS footprint halves, and with the register
+// budget of __launch_bounds__(256, 3) three workgroups are resident per CU
+// instead of two.  A list longer than one super-batch rebuilds the low half from
+// the table rows (L2 hits) for every further super-batch.
+// REGISTER BUDGET: k_scan_lean<16, 6, true> sits exactly at the 168 VGPRs of three
+// waves per SIMD, without scratch, and only because of opq() below.  Any edit of the
+// item loop, and any compiler update, can put spills back silently (scratch traffic
+// has cost this kernel 4x before): tests/test_scan_resources.py reads the built
+// code object and fails on scratch, on more than 168 VGPRs or on more than 53 KB of
+// LDS.  Re-check with -Rpass-analysis=kernel-resource-usage after touching it.
+template <int M, int JB, bool SPLIT>
+__global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
   constexpr int G = 4;
   constexpr int LUTN = M * 256;
   constexpr int NV = LUTN / 4 / 256;  // float4 per thread per table row
   static_assert(NV <= 4 && JB % 2 == 0, "lean scan: M <= 16");
-  __shared__ __attribute__((aligned(16))) float4 lut[LUTN];  // [m][j][g]
+  constexpr int NP = SPLIT ? 2 : 1;  // passes over the sub-quantizers
+  constexpr int NH = NV / NP;        // float4 per thread per table row and pass
+  constexpr int MH = M / NP;         // sub-quantizers per pass
+  static_assert(NV % NP == 0 && (M / 4) % NP == 0, "lean scan: a pass is whole float4 rows and whole code words");
+  constexpr bool kPre = kScanPrefetch && !SPLIT;
+  __shared__ __attribute__((aligned(16))) float4 lut[LUTN / NP];  // [m of the pass][j][g]
   __shared__ int s_next;
   __shared__ int32_t s_wb[G];
   __shared__ int s_ws[8];
@@ -2610,7 +2647,14 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
   const float inv_np = 1.0f / (float)a.nprobe;
   const int rg = lane >> 4, re = lane & 15;  // row-packed top-k: lane 16 g + e = entry e of pair g
   const int2 nn = fused_plan_prefix(pl, nloc, G, s_ex[0], s_ex[1], s_ord, s_ws);
-  const int n_items0 = nn.x, n_items = nn.x + nn.y;
+  const int n_items0 = nn.x, n_items = SPLIT ? __builtin_amdgcn_readfirstlane(nn.x + nn.y) : nn.x + nn.y;
+  // SPLIT, opq(tid) / opq(lane): per-thread addresses and masks of the item loop are
+  // formed where they are used -- hoisted out of the loop they would be held in VGPRs
+  // (pointers in two) across it, over the register budget of three waves per SIMD
+  auto opq = [&](int v) __attribute__((always_inline)) {
+    if constexpr (SPLIT) asm volatile("" : "+v"(v));
+    return v;
+  };
 
   Item<G> it;
   auto unpack = [&](const Rec& rc) __attribute__((always_inline)) {
@@ -2639,7 +2683,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
     for (int g = 0; g < G; g++) it.q[g] = div_small((g < it.cnt ? it.pair[g] : it.pair[0]), a.nprobe, inv_np);
   };
   auto fetch_rec = [&](int idx) __attribute__((always_inline)) {
-    return fused_record(a, pl, nloc, idx, n_items0, s_ex[0], s_ex[1], s_ord, G, lane);
+    return fused_record(a, pl, nloc, idx, n_items0, s_ex[0], s_ex[1], s_ord, G, opq(lane));
   };
 
   if (tid == 0) {
@@ -2658,43 +2702,46 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
   // of stalling the next LUT build (the build waited ~5 000 cycles for them, r04
   // stamps: about the per-CU Infinity-Cache rate).
   uint64_t tw[G];  // the queries' tau words, decoded after barrier B
-  float4 b1[NV], b3[NV][G];
+  float4 b1[NH], b3[NH][G];  // (SPLIT: one pass's rows at a time)
   // (with kScanPrefetch the T3 rows, 64 of the 80 KB, come ahead; the T1 row is
   // loaded at the item start: all 80 KB ahead left too few VGPRs at JB 6)
+  // (prefetch_t3, load_t1: the one-pass form only -- b1 / b3 hold NH < NV rows under SPLIT)
   auto prefetch_t3 = [&](const int (&q)[G]) __attribute__((always_inline)) {
+    if constexpr (!SPLIT) {
 #pragma unroll
-    for (int g = 0; g < G; g++) tw[g] = tau_load(pl, q[g]);
+      for (int g = 0; g < G; g++) tw[g] = tau_load(pl, q[g]);
 #pragma unroll
-    for (int e = 0; e < NV; e++) {
-      const int v = e * 256 + tid;
+      for (int e = 0; e < NV; e++) {
+        const int v = e * 256 + tid;
 #pragma unroll
-      for (int g = 0; g < G; g++) b3[e][g] = reinterpret_cast<const float4*>(a.T3 + (int64_t)q[g] * LUTN)[v];
+        for (int g = 0; g < G; g++) b3[e][g] = reinterpret_cast<const float4*>(a.T3 + (int64_t)q[g] * LUTN)[v];
+      }
     }
   };
   auto load_t1 = [&](int l, int q0) __attribute__((always_inline)) {
-    const float4* T1l = reinterpret_cast<const float4*>(ip ? a.T3 + (int64_t)q0 * LUTN : a.T1 + (int64_t)l * LUTN);
+    if constexpr (!SPLIT) {
+      const float4* T1l = reinterpret_cast<const float4*>(ip ? a.T3 + (int64_t)q0 * LUTN : a.T1 + (int64_t)l * LUTN);
 #pragma unroll
-    for (int e = 0; e < NV; e++) b1[e] = T1l[e * 256 + tid];
-  };
-  if (kScanPrefetch && cur >= 0) prefetch_t3(it.q);
-  int it_no = 0;  // (DIAG stamps)
-  (void)it_no;
-  while (cur >= 0) {
-    __syncthreads();  // (A) every wave is done with the previous LUT and has read s_next
-    DIAG(0, __builtin_amdgcn_s_memtime());
-    int tnext;
-    if (tid == 0) tnext = atomicAdd(pl.hdr + 2, 1);
-    if (!kScanPrefetch) prefetch_t3(it.q);
-    load_t1(it.l, it.q[0]);
-    const int n = it.n;
-    const uint8_t* lc = a.codes + it.beg * M;
-#pragma unroll
-    for (int j = 0; j < JB; j++) {  // the item's first JB x 256 codes, in flight during the LUT stores
-      const int i = j * 256 + wave * 64 + lane;
-      cw[j].load(lc + (int64_t)(i < n ? i : 0) * M);
+      for (int e = 0; e < NV; e++) b1[e] = T1l[e * 256 + tid];
     }
+  };
+  // pass hf's table rows of the current item (SPLIT), and their LUT entries
+  auto load_rows = [&](int hf) __attribute__((always_inline)) {
+    const int tid = opq(threadIdx.x);
+    const float4* T1l =
+        reinterpret_cast<const float4*>(ip ? a.T3 + (int64_t)it.q[0] * LUTN : a.T1 + (int64_t)it.l * LUTN);
 #pragma unroll
-    for (int e = 0; e < NV; e++) {
+    for (int e = 0; e < NH; e++) {
+      const int v = (hf * NH + e) * 256 + tid;
+#pragma unroll
+      for (int g = 0; g < G; g++) b3[e][g] = reinterpret_cast<const float4*>(a.T3 + (int64_t)it.q[g] * LUTN)[v];
+      b1[e] = T1l[v];
+    }
+  };
+  auto store_rows = [&]() __attribute__((always_inline)) {
+    const int tid = opq(threadIdx.x);
+#pragma unroll
+    for (int e = 0; e < NH; e++) {
       const int v = e * 256 + tid;
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -2707,8 +2754,33 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
         lut[4 * v + c] = o;
       }
     }
+  };
+  if (kPre && cur >= 0) prefetch_t3(it.q);
+  int it_no = 0;  // (DIAG stamps)
+  (void)it_no;
+  while (cur >= 0) {
+    __syncthreads();  // (A) every wave is done with the previous LUT and has read s_next
+    DIAG(0, __builtin_amdgcn_s_memtime());
+    int tnext;
+    if (tid == 0) tnext = atomicAdd(pl.hdr + 2, 1);
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int g = 0; g < G; g++) tw[g] = tau_load(pl, it.q[g]);
+      load_rows(0);
+    } else {
+      if (!kPre) prefetch_t3(it.q);
+      load_t1(it.l, it.q[0]);
+    }
+    const int n = it.n;
+    const uint8_t* lc = a.codes + it.beg * M;
+#pragma unroll
+    for (int j = 0; j < JB; j++) {  // the item's first JB x 256 codes, in flight during the LUT stores
+      const int i = j * 256 + wave * 64 + lane;
+      cw[j].load(lc + (int64_t)(i < n ? i : 0) * M);
+    }
+    store_rows();
     if (tid == 0) s_next = tnext < n_items ? tnext : -1;
-    if (tid < G) s_wb[tid] = f2ord(kInf);
+    if (const int t = opq(tid); t < G) s_wb[t] = f2ord(kInf);
     __syncthreads();  // (B) the LUT, s_next and s_wb are visible
     DIAG(1, __builtin_amdgcn_s_memtime());
     const int nxt = s_next;
@@ -2782,40 +2854,71 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
       // G keys per code: dis0 + sum_m LUT[m][code_m], sequential in m (the oracle's order);
       // two chunks at a time (their 2 M gathers interleaved), a lone last chunk alone
       float dis[JB][G];
+      // pass hf: sub-quantizers hf MH .. hf MH + MH - 1 of every chunk, from the LUT of that pass
+      auto gather = [&](int hf) __attribute__((always_inline)) {
 #pragma unroll
-      for (int jd = 0; jd < JB / 2; jd++) {
-        if (2 * jd + 1 < tn) {
-          CodeWords<M> cc[2] = {cw[2 * jd], cw[2 * jd + 1]};
+        for (int jd = 0; jd < JB / 2; jd++) {
+          if (2 * jd + 1 < tn) {
+            uint32_t cc[2][MH / 4];
 #pragma unroll
-          for (int h = 0; h < 2; h++)
+            for (int h = 0; h < 2; h++)
 #pragma unroll
-            for (int v = 0; v < M / 4; v++) asm volatile("" : "+v"(cc[h].w[v]));
+              for (int v = 0; v < MH / 4; v++) {
+                cc[h][v] = cw[2 * jd + h].w[hf * (MH / 4) + v];
+                asm volatile("" : "+v"(cc[h][v]));
+              }
+            if (hf == 0) {
 #pragma unroll
-          for (int h = 0; h < 2; h++)
+              for (int h = 0; h < 2; h++)
 #pragma unroll
-            for (int g = 0; g < G; g++) dis[2 * jd + h][g] = it.d0[g];
+                for (int g = 0; g < G; g++) dis[2 * jd + h][g] = it.d0[g];
+            }
 #pragma unroll
-          for (int m = 0; m < M; m++) {
+            for (int m = 0; m < MH; m++) {
 #pragma unroll
-            for (int h = 0; h < 2; h++) {
-              const float4 v = lut[m * 256 + cc[h].byte(m)];
+              for (int h = 0; h < 2; h++) {
+                const float4 v = lut[m * 256 + ((cc[h][m >> 2] >> ((m & 3) * 8)) & 0xffu)];
 #pragma unroll
-              for (int g = 0; g < G; g++) dis[2 * jd + h][g] = dis[2 * jd + h][g] + comp(v, g);
+                for (int g = 0; g < G; g++) dis[2 * jd + h][g] = dis[2 * jd + h][g] + comp(v, g);
+              }
+            }
+          } else if (2 * jd < tn) {
+            uint32_t cc[MH / 4];
+#pragma unroll
+            for (int v = 0; v < MH / 4; v++) {
+              cc[v] = cw[2 * jd].w[hf * (MH / 4) + v];
+              asm volatile("" : "+v"(cc[v]));
+            }
+            if (hf == 0) {
+#pragma unroll
+              for (int g = 0; g < G; g++) dis[2 * jd][g] = it.d0[g];
+            }
+#pragma unroll
+            for (int m = 0; m < MH; m++) {
+              const float4 v = lut[m * 256 + ((cc[m >> 2] >> ((m & 3) * 8)) & 0xffu)];
+#pragma unroll
+              for (int g = 0; g < G; g++) dis[2 * jd][g] = dis[2 * jd][g] + comp(v, g);
             }
           }
-        } else if (2 * jd < tn) {
-          CodeWords<M> cc = cw[2 * jd];
-#pragma unroll
-          for (int v = 0; v < M / 4; v++) asm volatile("" : "+v"(cc.w[v]));
-#pragma unroll
-          for (int g = 0; g < G; g++) dis[2 * jd][g] = it.d0[g];
-#pragma unroll
-          for (int m = 0; m < M; m++) {
-            const float4 v = lut[m * 256 + cc.byte(m)];
-#pragma unroll
-            for (int g = 0; g < G; g++) dis[2 * jd][g] = dis[2 * jd][g] + comp(v, g);
-          }
         }
+      };
+      if constexpr (SPLIT) {
+        if (sb > 0) {  // a further super-batch of the list: the low half again, from the table rows
+          load_rows(0);
+          __syncthreads();  // every wave has gathered the previous super-batch's high half
+          store_rows();
+          __syncthreads();
+        }
+        gather(0);
+        // the high half's rows are loaded after the low half's gathers: ahead of them
+        // their 40 registers do not fit beside dis[] and cw[] at three waves per SIMD
+        load_rows(1);
+        __syncthreads();  // every wave has gathered the low half
+        store_rows();
+        __syncthreads();
+        gather(1);
+      } else {
+        gather(0);
       }
       DIAG_ONLY(asm volatile("" ::"v"(dis[0][0]), "v"(dis[JB - 1][G - 1])); const uint64_t tg1 = __builtin_amdgcn_s_memtime(); d_gather += tg1 - tg0;)
       if (!last_sb) {  // the next super-batch's codes, in flight during this one's admission
@@ -2825,7 +2928,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
           cw[j].load(lc + (int64_t)(i < n ? i : 0) * M);
         }
       }
-      if (kScanPrefetch && last_sb && nxt >= 0) {
+      if (kPre && last_sb && nxt >= 0) {
         // the next item: its record unpacked here (its load is the oldest in flight, so
         // this waits for nothing younger), then its table rows and bounds loaded, in
         // flight during this item's admission, partial writes and barrier (see prefetch)
@@ -2895,11 +2998,11 @@ __global__ __launch_bounds__(256, 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
     // the next item's fields (without the prefetch: its record load is older than the
     // stores and atomics below, so this waits for it alone), then this item's bounds
     // and partial lists
-    if (!kScanPrefetch && nxt >= 0) unpack(nrec);
+    if (!kPre && nxt >= 0) unpack(nrec);
     publish();
     if (st) {
       const bool empty = rk == kKcNone;
-      pl.part[slot * pl.ks + re] =
+      pl.part[slot * pl.ks + opq(re)] =
           part_rec(empty ? FLT_MAX : kc_key(rk), part_tag(pl.epoch, slot) | xcc_tag(), empty ? -1 : beg + (int64_t)(uint32_t)rk);
     }
     DIAG(3, __builtin_amdgcn_s_memtime());
@@ -4185,16 +4288,51 @@ int list_scan_max_items(int64_t npairs, int nloc, int G) {
   return (int)v;
 }
 
-int scan_lists_grid(int M, int k, int free_cus) {
+// Whether k_scan_lean scans the lists of a search.  The one predicate behind both the
+// kernel launch_scan_lists picks and the size of its persistent grid.
+static bool scan_uses_lean(int M, int k, bool fused) {
+  return kScanLean && fused && k <= 16 && (M == 8 || M == 16) && list_scan_group(M, k) == 4;
+}
+
+// workgroups of k_scan_lean<M> resident per CU: the runtime's occupancy of the
+// instantiation that is launched (registers and LDS), asked once
+static int lean_wgs_per_cu(int M) {
+  static int cache[2] = {0, 0};
+  int& c = cache[M == 16 ? 1 : 0];
+  if (!c) {
+    int n = 0;
+    const hipError_t e =
+        M == 16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<16, lean_jb(16), lean_split(16)>, 256, 0)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<8, lean_jb(8), lean_split(8)>, 256, 0);
+    c = e == hipSuccess && n > 0 ? n : (lean_split(M) ? 3 : 2);  // (no answer: the launch bounds)
+  }
+  return c;
+}
+
+// CUs the persistent scan leaves to the other streams while batches are in flight.
+// The one-pass scans share a CU with the next batch's coarse GEMM (two 200-register
+// waves per SIMD leave it room), so 16 CUs for the merges are enough (r06x sweep).
+// Three 168-register waves of the two-pass scan leave a SIMD 8 registers, so a grid
+// that fills the CUs three deep shuts the GEMM out: 0 - 64 free CUs measured 6 - 11 %
+// slower than the one-pass scan.  96 free CUs, a grid of 480 workgroups like the
+// one-pass scan's, which the dispatcher spreads about two per CU, is the one point
+// that is not slower; the in-flight step is then the one-pass scan's within spread
+// (profiles/scan_split_lut.md).
+int scan_inflight_free_cus(int M, int k, bool fused) {
+  return scan_uses_lean(M, k, fused) && lean_split(M) ? kInflightFreeCusSplit : kInflightFreeCus;
+}
+
+int scan_lists_grid(int M, int k, bool fused, int free_cus) {
   static int cus = 0;
   if (!cus) {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     cus = n;
   }
-  // workgroups per CU the LDS allows (LUTs, candidate queues, fused-plan prefix), at most 3
+  // workgroups per CU: k_scan_lean's occupancy; k_scan_lists: what the LDS allows
+  // (LUTs, candidate queues, fused-plan prefix), at most 3
   const int lds = M * 256 * 4 * list_scan_group(M, k) + 4 * QCAP * 8 + 6 * kFusedPlanLists + 96;
-  const int per_cu = std::max(1, std::min(3, 160 * 1024 / lds));
+  const int per_cu = scan_uses_lean(M, k, fused) ? lean_wgs_per_cu(M) : std::max(1, std::min(3, 160 * 1024 / lds));
 #ifdef SCAN_GRID_QUARTERS  // (A/B builds: workgroups per CU in quarters, e.g. 7 = 1.75 per CU)
   if (per_cu == 2) return std::max(8, (SCAN_GRID_QUARTERS * cus / 4 + 7) / 8 * 8);
 #endif
@@ -4230,9 +4368,9 @@ static void launch_lists_MR(const ScanArgs& a, const ListPlan& pl, hipStream_t s
   // (M > 32: 4 chunks, r04 A/B vs 2: C3 scan 643 -> 624 us, C4 214 -> 210 us)
   constexpr int JB = M <= 16 ? 6 : 4;
   if (ev) (void)hipEventRecord(ev[0], s);
-  if constexpr (G == 4 && R == 1) {
-    if (a.k <= 16 && pl.fused && kScanLean && M <= 16) {  // (row-packed top-k, insertion instead of a queue)
-      hipLaunchKernelGGL((k_scan_lean<M, kLeanJB>), dim3((unsigned)pl.grid), dim3(256), 0, s, a, pl);
+  if constexpr (G == 4 && R == 1 && M <= 16) {
+    if (scan_uses_lean(M, a.k, pl.fused != 0)) {  // (row-packed top-k, insertion instead of a queue)
+      hipLaunchKernelGGL((k_scan_lean<M, lean_jb(M), lean_split(M)>), dim3((unsigned)pl.grid), dim3(256), 0, s, a, pl);
     } else if (a.k <= 16) {  // r03 A/B at C2: 115.1 vs 125.7 us
       hipLaunchKernelGGL((k_scan_lists<M, G, R, JB, true>), dim3((unsigned)pl.grid), dim3(256), 0, s, a, pl);
     } else {

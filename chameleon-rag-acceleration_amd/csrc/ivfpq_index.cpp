@@ -359,7 +359,9 @@ struct ivfpq_index {
     // and merge kernels (r06x sweep of the one-pass scans: C2 step -2.5 %;
     // DESIGN.md section 4); one batch at a time, and in the shard flow's preassigned
     // searches, where the sweep was inconclusive, it takes them all
-    pl.grid = scan_lists_grid(M, k, pl.fused != 0, leave_free ? scan_inflight_free_cus(M, k, pl.fused != 0) : 0);
+    // (and the four-pass scan is capped at scan_inflight_wgs_per_cu() workgroups per CU)
+    pl.grid = scan_lists_grid(M, k, pl.fused != 0, leave_free ? scan_inflight_free_cus(M, k, pl.fused != 0) : 0,
+                              leave_free ? scan_inflight_wgs_per_cu(M, k, pl.fused != 0) : 0, &pl.lds_pad);
     return pl;
   }
 

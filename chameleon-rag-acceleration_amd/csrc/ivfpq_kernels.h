@@ -126,6 +126,7 @@ struct ListPlan {
   uint32_t* evlog;   // [kEvLog][8] the first stale-entry events (k_merge_probes log_stale)
   int fault = 0;     // test hook (ivfpq_set_fault_injection): > 0 = slots with slot % fault == 1 are not written
   int grid;          // persistent list-scan workgroups (multiple of 8)
+  int lds_pad = 0;   // dynamic LDS of the k_scan_lean launch, unused by the kernel (scan_lists_grid's residency cap)
   const int32_t* order = nullptr;  // [nloc] item order of the lists within a kind (nullable = list order)
   int fused = 0;     // 1: the list scan derives its items from cnt/bucket (no k_plan_items launch, recs unused)
   int ks = 0;        // partial-list stride in entries (part_stride(k))
@@ -168,8 +169,11 @@ int list_scan_group(int M, int k);  // pairs per work item (G) used for (M, k)
 int list_scan_max_items(int64_t npairs, int nloc, int G);
 // persistent grid on all but free_cus CUs: the workgroups per CU resident of the kernel
 // that launch_scan_lists picks for (M, k, fused = ListPlan::fused)
-int scan_lists_grid(int M, int k, bool fused, int free_cus = 0);
-int scan_inflight_free_cus(int M, int k, bool fused);  // free_cus of a search with batches in flight
+// wgs_cap (> 0, the four-pass k_scan_lean only): at most that many workgroups per CU;
+// *lds_pad (nullable: no cap) receives the dynamic LDS the launch must ask for (ListPlan::lds_pad)
+int scan_lists_grid(int M, int k, bool fused, int free_cus = 0, int wgs_cap = 0, int* lds_pad = nullptr);
+int scan_inflight_free_cus(int M, int k, bool fused);    // free_cus of a search with batches in flight
+int scan_inflight_wgs_per_cu(int M, int k, bool fused);  // wgs_cap of a search with batches in flight
 bool scan_supported_M(int M);
 // list scan + probe merge; ev_lists (nullable): two events recorded around the list-scan kernel alone
 void launch_scan_lists(const ScanArgs& a, const ListPlan& plan, hipStream_t s, hipEvent_t* ev_lists = nullptr);

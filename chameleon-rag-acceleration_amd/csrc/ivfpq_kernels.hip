@@ -2566,17 +2566,29 @@ constexpr bool kScanPrefetch = SCAN_PREFETCH != 0;  // (-DSCAN_PREFETCH=0: table
 #ifndef SCAN_LEAN_SPLIT_JB
 #define SCAN_LEAN_SPLIT_JB 6
 #endif
-// (-DSCAN_LEAN_SPLIT=0: the one-pass k_scan_lean, whole LUT in LDS, two workgroups per CU)
-// The two-pass form is for M = 16 only.  The one-pass M = 8 kernel is already resident
+#ifndef SCAN_LEAN_PASSES
+#define SCAN_LEAN_PASSES 2
+#endif
+static_assert(SCAN_LEAN_PASSES == 2 || SCAN_LEAN_PASSES == 4, "the split k_scan_lean has two or four passes");
+// (-DSCAN_LEAN_SPLIT=0: the one-pass k_scan_lean, whole LUT in LDS, two workgroups per CU;
+//  -DSCAN_LEAN_PASSES=4: the four-pass form, a quarter of the LUT per pass, compiled for four
+//  workgroups per CU.  It measured no faster than the two-pass form with batches in flight and
+//  1 - 5 % slower one batch at a time, so the two-pass form ships: profiles/scan_four_pass.md)
+// The split forms are for M = 16 only.  The one-pass M = 8 kernel is already resident
 // three per CU (158 VGPRs, 38,976 B), so the split cannot raise its residency and only
 // adds two barriers per super-batch: it measured 85.5 vs 84.6 us (profiles/scan_split_lut.md).
 constexpr bool lean_split(int M) { return SCAN_LEAN_SPLIT != 0 && M == 16; }
 // code chunks per super-batch of k_scan_lean
 constexpr int lean_jb(int M) { return lean_split(M) ? SCAN_LEAN_SPLIT_JB : SCAN_LEAN_JB; }
+// passes of k_scan_lean over the sub-quantizers
+constexpr int lean_passes(int M) { return lean_split(M) ? SCAN_LEAN_PASSES : 1; }
 // CUs the persistent scan leaves to the other streams while batches are in flight
 // (one-pass scans: r06x sweep, C2 step -2.5 % with 16; two-pass scan: the sweeps of
 // profiles/scan_split_lut.md, see scan_inflight_free_cus)
 constexpr int kInflightFreeCus = 16, kInflightFreeCusSplit = 96;
+// the four-pass scan (-DSCAN_LEAN_PASSES=4) in flight: free CUs and workgroups per CU
+// (0: as many as fit), the best point of the sweep in profiles/scan_four_pass.md
+constexpr int kInflightFreeCus4 = 64, kInflightWgsPerCu4 = 3;
 
 // ------------------------------------------------ lean list scan (k <= 16)
 // k_scan_lean: the C2 configuration (G = 4 pairs per item, k <= 16, M <= 16,
@@ -2614,24 +2626,42 @@ __device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v) {  // lane i <- lan
 // budget of __launch_bounds__(256, 3) three workgroups are resident per CU
 // instead of two.  A list longer than one super-batch rebuilds the low half from
 // the table rows (L2 hits) for every further super-batch.
-// REGISTER BUDGET: k_scan_lean<16, 6, true> sits exactly at the 168 VGPRs of three
-// waves per SIMD, without scratch, and only because of opq() below.  Any edit of the
-// item loop, and any compiler update, can put spills back silently (scratch traffic
-// has cost this kernel 4x before): tests/test_scan_resources.py reads the built
-// code object and fails on scratch, on more than 168 VGPRs or on more than 53 KB of
-// LDS.  Re-check with -Rpass-analysis=kernel-resource-usage after touching it.
-template <int M, int JB, bool SPLIT>
-__global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
+// NP = 4 (-DSCAN_LEAN_PASSES=4) does the same in four passes of four sub-quantizers.
+// Pass p gathers with word p of each 16-byte code, loaded for that pass alone into
+// cq[JB] after pass p - 1's gathers, instead of the whole codes waiting in cw[JB]; the
+// LUT quarters alternate between two 16 KB buffers, pass p + 1's rows are loaded ahead
+// of pass p's gathers, and there is one barrier per pass (FOUR below).
+// REGISTER BUDGET, without scratch in every form:
+//   NP = 2 (shipped): 146 VGPRs of the 168 of three waves per SIMD, 38,976 B of LDS;
+//   NP = 4: 120 VGPRs of the 128 of four waves per SIMD, 38,976 B.
+// They get there only through opq() below and through readfirstlane on the item's query
+// indices in unpack() (uniform, but computed on the VALU: it.q[] and its copies qix[]
+// otherwise take eight VGPRs across the scan; the two-pass form sat at exactly 168 before).
+// Any edit of the item loop, and any compiler update, can put spills back silently
+// (scratch traffic has cost this kernel 4x before): tests/test_scan_resources.py and
+// tests/test_scan_resources_fourpass.py read the built code object and fail on scratch,
+// on more than 168 VGPRs or on more than 53 KB of LDS (three workgroups per CU).
+// Re-check with -Rpass-analysis=kernel-resource-usage after touching it.
+template <int M, int JB, bool SPLIT, int NP = SPLIT ? 2 : 1>
+__global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lean(ScanArgs a, ListPlan pl) {
   constexpr int G = 4;
   constexpr int LUTN = M * 256;
   constexpr int NV = LUTN / 4 / 256;  // float4 per thread per table row
   static_assert(NV <= 4 && JB % 2 == 0, "lean scan: M <= 16");
-  constexpr int NP = SPLIT ? 2 : 1;  // passes over the sub-quantizers
-  constexpr int NH = NV / NP;        // float4 per thread per table row and pass
-  constexpr int MH = M / NP;         // sub-quantizers per pass
+  static_assert(SPLIT ? NP == 2 || NP == 4 : NP == 1, "lean scan: one pass, or the LUT split in two or four");
+  constexpr int NH = NV / NP;  // float4 per thread per table row and pass
+  constexpr int MH = M / NP;   // sub-quantizers per pass
   static_assert(NV % NP == 0 && (M / 4) % NP == 0, "lean scan: a pass is whole float4 rows and whole code words");
+  // FOUR (the four-pass form): a pass gathers with one 32-bit word of each code, loaded
+  // for that pass alone; otherwise the whole codes wait in registers across the passes.
+  // And two LUT buffers, pass p in buffer p & 1: pass p + 1's rows are loaded ahead of
+  // pass p's gathers and stored into the other buffer right after them, so there is one
+  // barrier per pass and no table-row round trip between two passes
+  constexpr bool FOUR = NP == 4;
+  static_assert(!FOUR || MH == 4, "lean scan, four passes: one code word per pass");
+  constexpr int LB = LUTN / NP;  // float4 per LUT buffer
   constexpr bool kPre = kScanPrefetch && !SPLIT;
-  __shared__ __attribute__((aligned(16))) float4 lut[LUTN / NP];  // [m of the pass][j][g]
+  __shared__ __attribute__((aligned(16))) float4 lut[(FOUR ? 2 : 1) * LB];  // [buffer][m of the pass][j][g]
   __shared__ int s_next;
   __shared__ int32_t s_wb[G];
   __shared__ int s_ws[8];
@@ -2680,7 +2710,12 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
       for (int g = 0; g < G; g++) it.pair[g] = 0;
     }
 #pragma unroll
-    for (int g = 0; g < G; g++) it.q[g] = div_small((g < it.cnt ? it.pair[g] : it.pair[0]), a.nprobe, inv_np);
+    for (int g = 0; g < G; g++) {
+      // (SPLIT: the quotient comes from the VALU; readfirstlane returns the uniform value to
+      // an SGPR, or it.q[] and its copies qix[] take eight VGPRs across the scan)
+      const int q = div_small((g < it.cnt ? it.pair[g] : it.pair[0]), a.nprobe, inv_np);
+      it.q[g] = SPLIT ? __builtin_amdgcn_readfirstlane(q) : q;
+    }
   };
   auto fetch_rec = [&](int idx) __attribute__((always_inline)) {
     return fused_record(a, pl, nloc, idx, n_items0, s_ex[0], s_ex[1], s_ord, G, opq(lane));
@@ -2693,7 +2728,8 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
   __syncthreads();
   int cur = s_next;
   if (cur >= 0) unpack(fetch_rec(cur));
-  CodeWords<M> cw[JB];
+  CodeWords<M> cw[FOUR ? 1 : JB];
+  uint32_t cq[FOUR ? JB : 1];  // (FOUR) the current pass's word of every chunk's code
   // An item's table rows: T1[l] (IP: a T3 row, ignored) and its G pairs' T3 rows,
   // one round trip, and its queries' bounds tau_q.  With kScanPrefetch they are
   // loaded for the NEXT item right after the current item's last gathers (its
@@ -2738,7 +2774,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
       b1[e] = T1l[v];
     }
   };
-  auto store_rows = [&]() __attribute__((always_inline)) {
+  auto store_rows = [&](int buf) __attribute__((always_inline)) {
     const int tid = opq(threadIdx.x);
 #pragma unroll
     for (int e = 0; e < NH; e++) {
@@ -2751,7 +2787,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
           const float x3 = comp(b3[e][g], c);
           setc(o, g, ip ? -x3 : __builtin_fmaf(x3, -2.0f, comp(b1[e], c)));  // (oracle: one rounding)
         }
-        lut[4 * v + c] = o;
+        lut[buf * LB + 4 * v + c] = o;
       }
     }
   };
@@ -2773,12 +2809,24 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
     }
     const int n = it.n;
     const uint8_t* lc = a.codes + it.beg * M;
+    // the codes of the super-batch at sb0 for pass p: chunk j holds codes sb0 + 256 j +
+    // 64 wave + lane (past the list's end: code 0 again, never admitted).  FOUR: word p
+    // of each code alone, 4 bytes at the 16-byte stride of the 16-byte load and inside
+    // the same code; otherwise (p = 0 only) the whole codes
+    auto load_codes = [&](int sb0, int p) __attribute__((always_inline)) {
+      const int i0 = sb0 + wave * 64 + opq(lane);
 #pragma unroll
-    for (int j = 0; j < JB; j++) {  // the item's first JB x 256 codes, in flight during the LUT stores
-      const int i = j * 256 + wave * 64 + lane;
-      cw[j].load(lc + (int64_t)(i < n ? i : 0) * M);
-    }
-    store_rows();
+      for (int j = 0; j < JB; j++) {
+        const int i = i0 + j * 256;
+        const uint8_t* pc = lc + (int64_t)(i < n ? i : 0) * M;
+        if constexpr (FOUR)
+          cq[j] = reinterpret_cast<const uint32_t*>(pc)[p];
+        else
+          cw[j].load(pc);
+      }
+    };
+    load_codes(0, 0);  // the item's first JB x 256 codes, in flight during the LUT stores
+    store_rows(0);
     if (tid == 0) s_next = tnext < n_items ? tnext : -1;
     if (const int t = opq(tid); t < G) s_wb[t] = f2ord(kInf);
     __syncthreads();  // (B) the LUT, s_next and s_wb are visible
@@ -2856,6 +2904,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
       float dis[JB][G];
       // pass hf: sub-quantizers hf MH .. hf MH + MH - 1 of every chunk, from the LUT of that pass
       auto gather = [&](int hf) __attribute__((always_inline)) {
+        const int lb = FOUR ? (hf & 1) * LB : 0;
 #pragma unroll
         for (int jd = 0; jd < JB / 2; jd++) {
           if (2 * jd + 1 < tn) {
@@ -2864,7 +2913,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
             for (int h = 0; h < 2; h++)
 #pragma unroll
               for (int v = 0; v < MH / 4; v++) {
-                cc[h][v] = cw[2 * jd + h].w[hf * (MH / 4) + v];
+                cc[h][v] = FOUR ? cq[2 * jd + h] : cw[FOUR ? 0 : 2 * jd + h].w[hf * (MH / 4) + v];
                 asm volatile("" : "+v"(cc[h][v]));
               }
             if (hf == 0) {
@@ -2877,7 +2926,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
             for (int m = 0; m < MH; m++) {
 #pragma unroll
               for (int h = 0; h < 2; h++) {
-                const float4 v = lut[m * 256 + ((cc[h][m >> 2] >> ((m & 3) * 8)) & 0xffu)];
+                const float4 v = lut[lb + m * 256 + ((cc[h][m >> 2] >> ((m & 3) * 8)) & 0xffu)];
 #pragma unroll
                 for (int g = 0; g < G; g++) dis[2 * jd + h][g] = dis[2 * jd + h][g] + comp(v, g);
               }
@@ -2886,7 +2935,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
             uint32_t cc[MH / 4];
 #pragma unroll
             for (int v = 0; v < MH / 4; v++) {
-              cc[v] = cw[2 * jd].w[hf * (MH / 4) + v];
+              cc[v] = FOUR ? cq[2 * jd] : cw[FOUR ? 0 : 2 * jd].w[hf * (MH / 4) + v];
               asm volatile("" : "+v"(cc[v]));
             }
             if (hf == 0) {
@@ -2895,39 +2944,55 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_scan_lean(ScanArgs a, Li
             }
 #pragma unroll
             for (int m = 0; m < MH; m++) {
-              const float4 v = lut[m * 256 + ((cc[m >> 2] >> ((m & 3) * 8)) & 0xffu)];
+              const float4 v = lut[lb + m * 256 + ((cc[m >> 2] >> ((m & 3) * 8)) & 0xffu)];
 #pragma unroll
               for (int g = 0; g < G; g++) dis[2 * jd][g] = dis[2 * jd][g] + comp(v, g);
             }
           }
         }
       };
-      if constexpr (SPLIT) {
-        if (sb > 0) {  // a further super-batch of the list: the low half again, from the table rows
+      if constexpr (FOUR) {
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+          // the pass after this one: p + 1, or pass 0 of the list's next super-batch
+          const bool more = p + 1 < NP || !last_sb;
+          const int pn = (p + 1) % NP;
+          if (more) load_rows(pn);
+          gather(p);
+          if (more) {
+            // its word of every code into the registers of the word just gathered with,
+            // its LUT into the buffer that pass p - 1 was gathered from: every wave has
+            // passed the barrier behind pass p's LUT, and so is done with pass p - 1
+            load_codes(p + 1 < NP ? sb : sb + 256 * JB, pn);
+            store_rows(pn & 1);
+            __syncthreads();
+          }
+        }
+      } else if constexpr (SPLIT) {
+        if (sb > 0) {  // a further super-batch of the list: pass 0 again, from the table rows
           load_rows(0);
-          __syncthreads();  // every wave has gathered the previous super-batch's high half
-          store_rows();
+          __syncthreads();  // every wave has gathered the previous super-batch's last pass
+          store_rows(0);
           __syncthreads();
         }
         gather(0);
-        // the high half's rows are loaded after the low half's gathers: ahead of them
-        // their 40 registers do not fit beside dis[] and cw[] at three waves per SIMD
-        load_rows(1);
-        __syncthreads();  // every wave has gathered the low half
-        store_rows();
-        __syncthreads();
-        gather(1);
+#pragma unroll
+        for (int p = 1; p < NP; p++) {
+          // pass p's rows are loaded after pass p - 1's gathers: ahead of them their
+          // registers do not fit beside dis[] and cw[] at three waves per SIMD
+          load_rows(p);
+          __syncthreads();  // every wave has gathered pass p - 1
+          store_rows(0);
+          __syncthreads();
+          gather(p);
+        }
       } else {
         gather(0);
       }
       DIAG_ONLY(asm volatile("" ::"v"(dis[0][0]), "v"(dis[JB - 1][G - 1])); const uint64_t tg1 = __builtin_amdgcn_s_memtime(); d_gather += tg1 - tg0;)
-      if (!last_sb) {  // the next super-batch's codes, in flight during this one's admission
-#pragma unroll
-        for (int j = 0; j < JB; j++) {
-          const int i = sb + 256 * JB + j * 256 + wave * 64 + lane;
-          cw[j].load(lc + (int64_t)(i < n ? i : 0) * M);
-        }
-      }
+      // the next super-batch's codes, in flight during this one's admission (FOUR: their
+      // pass-0 words, loaded behind the last pass's gathers above)
+      if (!FOUR && !last_sb) load_codes(sb + 256 * JB, 0);
       if (kPre && last_sb && nxt >= 0) {
         // the next item: its record unpacked here (its load is the oldest in flight, so
         // this waits for nothing younger), then its table rows and bounds loaded, in
@@ -4302,9 +4367,21 @@ static int lean_wgs_per_cu(int M) {
   if (!c) {
     int n = 0;
     const hipError_t e =
-        M == 16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<16, lean_jb(16), lean_split(16)>, 256, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<8, lean_jb(8), lean_split(8)>, 256, 0);
+        M == 16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<16, lean_jb(16), lean_split(16), lean_passes(16)>, 256, 0)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scan_lean<8, lean_jb(8), lean_split(8), lean_passes(8)>, 256, 0);
     c = e == hipSuccess && n > 0 ? n : (lean_split(M) ? 3 : 2);  // (no answer: the launch bounds)
+  }
+  return c;
+}
+
+// static LDS of the launched k_scan_lean<16> (scan_lists_grid's residency cap), asked once
+static int lean_static_lds16() {
+  static int c = 0;
+  if (!c) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(
+        &fa, reinterpret_cast<const void*>(&k_scan_lean<16, lean_jb(16), lean_split(16), lean_passes(16)>));
+    c = e == hipSuccess && fa.sharedSizeBytes > 0 ? (int)fa.sharedSizeBytes : 16 * 256 * 16 / lean_passes(16) + 6208;
   }
   return c;
 }
@@ -4319,10 +4396,17 @@ static int lean_wgs_per_cu(int M) {
 // that is not slower; the in-flight step is then the one-pass scan's within spread
 // (profiles/scan_split_lut.md).
 int scan_inflight_free_cus(int M, int k, bool fused) {
-  return scan_uses_lean(M, k, fused) && lean_split(M) ? kInflightFreeCusSplit : kInflightFreeCus;
+  if (!(scan_uses_lean(M, k, fused) && lean_split(M))) return kInflightFreeCus;
+  return lean_passes(M) == 4 ? kInflightFreeCus4 : kInflightFreeCusSplit;
 }
 
-int scan_lists_grid(int M, int k, bool fused, int free_cus) {
+// Workgroups per CU of the scan while batches are in flight (0: as many as fit).  Only
+// the four-pass scan is capped (scan_lists_grid).
+int scan_inflight_wgs_per_cu(int M, int k, bool fused) {
+  return scan_uses_lean(M, k, fused) && lean_split(M) && lean_passes(M) == 4 ? kInflightWgsPerCu4 : 0;
+}
+
+int scan_lists_grid(int M, int k, bool fused, int free_cus, int wgs_cap, int* lds_pad) {
   static int cus = 0;
   if (!cus) {
     int dev = 0, n = 256;
@@ -4332,7 +4416,30 @@ int scan_lists_grid(int M, int k, bool fused, int free_cus) {
   // workgroups per CU: k_scan_lean's occupancy; k_scan_lists: what the LDS allows
   // (LUTs, candidate queues, fused-plan prefix), at most 3
   const int lds = M * 256 * 4 * list_scan_group(M, k) + 4 * QCAP * 8 + 6 * kFusedPlanLists + 96;
-  const int per_cu = scan_uses_lean(M, k, fused) ? lean_wgs_per_cu(M) : std::max(1, std::min(3, 160 * 1024 / lds));
+  int per_cu = scan_uses_lean(M, k, fused) ? lean_wgs_per_cu(M) : std::max(1, std::min(3, 160 * 1024 / lds));
+  // wgs_cap: fewer workgroups of the four-pass scan per CU than its registers and LDS
+  // allow, so that every SIMD keeps registers for the other streams' waves.  The
+  // dispatcher packs a CU as full as it can, so the cap is enforced by the launch:
+  // *lds_pad bytes of dynamic LDS, which the kernel never touches, make a workgroup
+  // take more than 160 KB / (cap + 1).  The index asks for a cap only with batches in
+  // flight.  IVFPQ_SCAN_WGS_PER_CU overrides it (A/B runs; 0 = no cap, 1 is taken as 2:
+  // a cap of 1 would need more LDS than a launch may ask for) and, like
+  // IVFPQ_SCAN_FREE_CUS below, applies to every search, one batch at a time included
+  if (lds_pad) *lds_pad = 0;
+  if (scan_uses_lean(M, k, fused) && lean_split(M) && lean_passes(M) == 4 && lds_pad) {
+    static int env_cap = -2;
+    if (env_cap == -2) {
+      const char* e = getenv("IVFPQ_SCAN_WGS_PER_CU");
+      env_cap = e ? std::max(0, atoi(e)) : -1;
+    }
+    if (env_cap >= 0) wgs_cap = env_cap;
+    if (wgs_cap == 1) wgs_cap = 2;
+    if (wgs_cap > 0 && wgs_cap < per_cu) {
+      const int want = 160 * 1024 / (wgs_cap + 1) + 2048;  // (2 KB: past any allocation granule)
+      *lds_pad = std::max(0, want - lean_static_lds16());
+      per_cu = wgs_cap;
+    }
+  }
 #ifdef SCAN_GRID_QUARTERS  // (A/B builds: workgroups per CU in quarters, e.g. 7 = 1.75 per CU)
   if (per_cu == 2) return std::max(8, (SCAN_GRID_QUARTERS * cus / 4 + 7) / 8 * 8);
 #endif
@@ -4370,7 +4477,9 @@ static void launch_lists_MR(const ScanArgs& a, const ListPlan& pl, hipStream_t s
   if (ev) (void)hipEventRecord(ev[0], s);
   if constexpr (G == 4 && R == 1 && M <= 16) {
     if (scan_uses_lean(M, a.k, pl.fused != 0)) {  // (row-packed top-k, insertion instead of a queue)
-      hipLaunchKernelGGL((k_scan_lean<M, lean_jb(M), lean_split(M)>), dim3((unsigned)pl.grid), dim3(256), 0, s, a, pl);
+      // (pl.lds_pad: dynamic LDS the kernel does not use, scan_lists_grid's residency cap)
+      hipLaunchKernelGGL((k_scan_lean<M, lean_jb(M), lean_split(M), lean_passes(M)>), dim3((unsigned)pl.grid), dim3(256),
+                         (size_t)pl.lds_pad, s, a, pl);
     } else if (a.k <= 16) {  // r03 A/B at C2: 115.1 vs 125.7 us
       hipLaunchKernelGGL((k_scan_lists<M, G, R, JB, true>), dim3((unsigned)pl.grid), dim3(256), 0, s, a, pl);
     } else {

@@ -1,10 +1,14 @@
 #!/bin/bash
 # Build A/B variants of libivfpq.so (compile-time experiment switches) into lib/var/<name>/.
 # Usage: build_variants.sh name:"-DFOO=1 -DBAR=2" ...   ; select one at run time with IVFPQ_LIB=<path>.
+# Without arguments: the variants that are kept in the tree behind a macro, so that they are compiled somewhere:
+#   fourpass  -DSCAN_LEAN_PASSES=4  (four-pass k_scan_lean, profiles/scan_four_pass.md)
+#   onepass   -DSCAN_LEAN_SPLIT=0   (one-pass k_scan_lean, profiles/scan_split_lut.md)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/chameleon-rag-acceleration_amd/csrc
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I$R/include -I$C"
+[ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0"
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   O=$R/chameleon-rag-acceleration_amd/lib/var/$name
@@ -12,8 +16,9 @@ for spec in "$@"; do
   /opt/rocm/bin/hipcc $F -mllvm -amdgpu-atomic-optimizer-strategy=None $defs -c -o "$O/k.o" "$C/ivfpq_kernels.hip" &
   /opt/rocm/bin/hipcc $F $defs -x hip -c -o "$O/i.o" "$C/ivfpq_index.cpp" &
   /opt/rocm/bin/hipcc $F $defs -c -o "$O/b.o" "$C/ivfpq_build.hip" &
+  /opt/rocm/bin/hipcc $F $defs -c -o "$O/p.o" "$C/pq_flat.hip" &
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$O/libivfpq.so" "$O/k.o" "$O/b.o" "$O/i.o"
-  rm -f "$O/k.o" "$O/i.o" "$O/b.o"
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$O/libivfpq.so" "$O/k.o" "$O/b.o" "$O/p.o" "$O/i.o"
+  rm -f "$O/k.o" "$O/i.o" "$O/b.o" "$O/p.o"
   echo "built $name ($defs)"
 done

@@ -86,9 +86,13 @@ void launch_pq_encode(const float* x, int64_t n, int d, const float* cent, const
 // A batch's (query, probe) pairs whose list is in the shard range [lo, hi) and
 // non-empty are bucketed by list: kind 0 = the query's first usable probe,
 // kind 1 = every other probe (cap slots per list and kind; a list holds at most
-// one pair per query).  Work items are (list, up to G pairs of one kind); all
-// kind-0 items are scheduled before kind-1 items, so each query's running
-// k-th key (tau) is usually known when its other probes are scanned.
+// one pair per query).  Work items are (list, up to G pairs): a list's pairs
+// form one sequence, kind 0 first, cut every G entries, so the free slots of
+// its last first-probe item are filled with its kind-1 pairs and the list has
+// ceil((c0 + c1) / G) items.  The ceil(c0 / G) items that hold kind-0 pairs are
+// LEAD items, the others REST items; all lead items are scheduled before any
+// rest item, so each query's running k-th key (tau) is usually known when its
+// other probes are scanned.  (-DPLAN_FILL_LEAD=0: items of one kind only.)
 // Stride of one per-wave partial list in `part`: k records of 16 B.
 inline int part_stride(int k) { return k; }
 
@@ -103,8 +107,10 @@ struct ListPlan {
   int32_t* cnt;      // [2][nloc] pair counts per kind; zero between batches (k_scan_lists re-zeroes)
   int2* bucket;      // [nloc][2 kinds][cap] (pair id q*nprobe+p, dis0 key bits)
   int cap;           // bucket slots per list (>= queries in the batch)
-  int32_t* recs;     // [max_items][16] work items: list, count, size, beg(2), pairs[4], dis0[4]
-  int32_t* hdr;      // [16]: n_items, n_items of kind 0, the list scan's work counter, 0...
+  int32_t* recs;     // [max_items][16] work items: list, count, size, beg(2), pairs[4], dis0[4], 0 lead / 1 rest
+  // [16]: n_items, n_items that are lead items (written by k_plan_items, or by the fused
+  // scan's first workgroup), the list scan's work counter, 0...
+  int32_t* hdr;
   int max_items;
   // [nq][nprobe][4 waves][k] per-wave sorted partial top-k, one 16-B record per entry:
   // {key bits, tag, global code position lo, hi} (position -1 = none; k <= 64 pads
@@ -127,7 +133,7 @@ struct ListPlan {
   int fault = 0;     // test hook (ivfpq_set_fault_injection): > 0 = slots with slot % fault == 1 are not written
   int grid;          // persistent list-scan workgroups (multiple of 8)
   int lds_pad = 0;   // dynamic LDS of the k_scan_lean launch, unused by the kernel (scan_lists_grid's residency cap)
-  const int32_t* order = nullptr;  // [nloc] item order of the lists within a kind (nullable = list order)
+  const int32_t* order = nullptr;  // [nloc] item order of the lists within the lead / the rest items (nullable = list order)
   int fused = 0;     // 1: the list scan derives its items from cnt/bucket (no k_plan_items launch, recs unused)
   int ks = 0;        // partial-list stride in entries (part_stride(k))
 };

@@ -17,7 +17,9 @@
 //    the batch: every (query, probe) pair is bucketed under its list, the
 //    query's first usable probe as kind 0, the others as kind 1;
 //  * k_scan_lists: persistent workgroups that derive their work items (list,
-//    up to G pairs, kind 0 first) from the per-list counts; per item the G
+//    up to G pairs: a list's kind-0 pairs first, the free slots of its last
+//    first-probe item filled with its kind-1 pairs; those lead items before
+//    every other item) from the per-list counts; per item the G
 //    LUTs (T1[list] - 2 T3[q], or -T3[q] for IP) are formed in LDS (the LUT
 //    never touches HBM), the list's PQ codes are streamed coalesced and every
 //    code is summed from M LDS lookups per query; top-k is fused into the scan
@@ -587,6 +589,44 @@ __device__ __forceinline__ void plan_pair(const ListPlan& pl, int nloc, int64_t 
   // a list holds at most one pair per query and kind, so s < cap (deduplicated rows)
   if (s < pl.cap) pl.bucket[((int64_t)(l - lo) * 2 + kind) * pl.cap + s] = make_int2(pair, __float_as_int(dis0));
   pl.pd0[pair] = dis0;  // the same dis0 for a merge that has to rescan the pair (repair_probe)
+}
+
+// Item composition of one list (both planners and the scans agree on it).  The
+// list's c0 kind-0 and c1 kind-1 pairs (clipped to cap) form one sequence, kind 0
+// first; item t holds entries t G .. t G + G - 1.  The first L = ceil(c0 / G)
+// items are LEAD items, scheduled before every REST item of any list, so a
+// query's first probe is still scanned in the first round; the last lead item
+// takes its f = L G - c0 free entries from kind-1 bucket slots 0 .. f - 1 instead
+// of leaving them empty, and rest item r starts at kind-1 slot r G + f.  The list
+// then has ceil((c0 + c1) / G) items instead of ceil(c0 / G) + ceil(c1 / G).
+// Which item carries a pair changes neither its keys nor its partial-list slot.
+// -DPLAN_FILL_LEAD=0: f = 0, items of one kind only (the composition before;
+// profiles/plan_fill_lead.md).  -DPLAN_FILL_OWN_MAX=n: only a last lead item with at
+// most n kind-0 pairs of its own is filled (measured with n = 2, not the default).
+#ifndef PLAN_FILL_LEAD
+#define PLAN_FILL_LEAD 1
+#endif
+#ifndef PLAN_FILL_OWN_MAX
+#define PLAN_FILL_OWN_MAX 4
+#endif
+constexpr bool kFillLead = PLAN_FILL_LEAD != 0;
+constexpr int kFillOwnMax = PLAN_FILL_OWN_MAX;
+
+struct ListItems {
+  int lead, rest;  // L, the rest items
+  int free;        // L G - c0, the entries the kind-0 pairs leave free in the last lead item
+  int filled;      // 1: they are filled with kind-1 pairs (f = free), 0: left empty (f = 0)
+  __device__ __forceinline__ int fill() const { return filled ? free : 0; }
+};
+__device__ __forceinline__ ListItems list_items(int c0, int c1, int cap, int G) {
+  c0 = min(c0, cap);
+  c1 = min(c1, cap);
+  ListItems r;
+  r.lead = (c0 + G - 1) / G;
+  r.free = r.lead * G - c0;
+  r.filled = kFillLead && G - r.free <= kFillOwnMax ? 1 : 0;
+  r.rest = (c1 - min(r.fill(), c1) + G - 1) / G;
+  return r;
 }
 
 // The query bound tau_q of this batch (an order-preserving int; "no bound" =
@@ -1469,8 +1509,8 @@ __global__ __launch_bounds__(256) void k_plan_count(const int64_t* __restrict__ 
   }
 }
 
-// Work items from the per-list counts.  Items of kind 0 occupy [0, N0), kind 1
-// [N0, N0 + N1), each in list order.  Small shard ranges (nloc <=
+// Work items from the per-list counts (list_items).  Lead items occupy [0, N0), rest
+// items [N0, N0 + N1), each in list order.  Small shard ranges (nloc <=
 // kPlanSmall): every workgroup builds the whole per-list item prefix in LDS
 // and writes the records of its 1024 items, one per thread (the grid covers
 // the item-count bound).  Large ranges: every workgroup takes 1024 lists,
@@ -1516,8 +1556,10 @@ __device__ __forceinline__ void block_scan2(int a, int b, int& ea, int& eb, int&
 
 __device__ __forceinline__ void write_item(const ListPlan& pl, const int64_t* __restrict__ list_off, int lo, int nloc,
                                            int G, int rec, int jj, int kind, int t) {
-  const int c = min(pl.cnt[kind * nloc + jj], pl.cap);
-  const int cnt = min(G, c - t * G);
+  // kind 0: lead item t of the list, kind 1: its rest item t (list_items)
+  const int c0 = min(pl.cnt[jj], pl.cap), c1 = min(pl.cnt[nloc + jj], pl.cap);
+  const ListItems li = list_items(c0, c1, pl.cap, G);
+  const int cnt = kind ? min(G, c1 - li.fill() - t * G) : min(G, (li.filled ? c0 + c1 : c0) - t * G);
   const int64_t l = lo + jj;
   const int64_t beg = list_off[l];
   int r[16];
@@ -1529,7 +1571,11 @@ __device__ __forceinline__ void write_item(const ListPlan& pl, const int64_t* __
 #pragma unroll
   for (int g = 0; g < 4; g++) {
     int2 v = make_int2(0, 0);
-    if (g < cnt) v = pl.bucket[((int64_t)jj * 2 + kind) * pl.cap + t * G + g];
+    if (g < cnt) {
+      const int s = t * G + g;  // lead: entry s of the sequence; rest: kind-1 slot s + f
+      const int bk = kind || s >= c0 ? 1 : 0;
+      v = pl.bucket[((int64_t)jj * 2 + bk) * pl.cap + (kind ? s + li.fill() : bk ? s - c0 : s)];
+    }
     r[5 + g] = v.x;
     r[9 + g] = v.y;
   }
@@ -1555,8 +1601,8 @@ __global__ __launch_bounds__(PLAN_T) void k_plan_items_small(ListPlan pl, const 
   for (int j0 = 0; j0 < nloc; j0 += PLAN_T) {
     const int j = j0 + tid;  // rank in the scheduling order
     const int jl = j < nloc ? (ord ? ord[j] : j) : 0;
-    const int a = j < nloc ? (min(pl.cnt[jl], pl.cap) + G - 1) / G : 0;
-    const int b = j < nloc ? (min(pl.cnt[nloc + jl], pl.cap) + G - 1) / G : 0;
+    const ListItems li = list_items(pl.cnt[jl], pl.cnt[nloc + jl], pl.cap, G);
+    const int a = j < nloc ? li.lead : 0, b = j < nloc ? li.rest : 0;
     int ea, eb, ta, tb;
     block_scan2(a, b, ea, eb, ta, tb, ws);
     if (j < nloc) {
@@ -1597,7 +1643,8 @@ __global__ __launch_bounds__(PLAN_T) void k_plan_items_big(ListPlan pl, const in
   const int my0 = blockIdx.x * PLAN_T;
   int t0 = 0, t1 = 0, p0 = 0, p1 = 0;
   for (int j = tid; j < nloc; j += PLAN_T) {
-    const int a = (min(pl.cnt[j], pl.cap) + G - 1) / G, b = (min(pl.cnt[nloc + j], pl.cap) + G - 1) / G;
+    const ListItems li = list_items(pl.cnt[j], pl.cnt[nloc + j], pl.cap, G);
+    const int a = li.lead, b = li.rest;
     t0 += a;
     t1 += b;
     if (j < my0) {
@@ -1609,8 +1656,9 @@ __global__ __launch_bounds__(PLAN_T) void k_plan_items_big(ListPlan pl, const in
   block_scan2(t0, t1, ea, eb, T0, T1, ws);
   block_scan2(p0, p1, ea, eb, P0, P1, ws);
   const int j = my0 + tid;
-  const int a = j < nloc ? (min(pl.cnt[j], pl.cap) + G - 1) / G : 0;
-  const int b = j < nloc ? (min(pl.cnt[nloc + j], pl.cap) + G - 1) / G : 0;
+  const int jc = j < nloc ? j : 0;
+  const ListItems lj = list_items(pl.cnt[jc], pl.cnt[nloc + jc], pl.cap, G);
+  const int a = j < nloc ? lj.lead : 0, b = j < nloc ? lj.rest : 0;
   int sa, sb;
   block_scan2(a, b, ea, eb, sa, sb, ws);
   ex0[tid] = ea;
@@ -1831,9 +1879,11 @@ struct Item {
   int q[G];  // query of pair g (pair / nprobe; absent pairs: the first pair's query)
 };
 
-// Persistent workgroups take work items from one counter: kind-0 items (each
-// query's first probe) first, so that a query's running k-th key tau_q is
-// usually known before its other probes are scanned.  A work item is (list l,
+// Persistent workgroups take work items from one counter: lead items (the ones
+// that hold the queries' first probes, list_items) first, so that a query's
+// running k-th key tau_q is usually known before its other probes are scanned
+// (the kind-1 pairs that fill a lead item are the exception: they are scanned
+// like first probes, against whatever bound exists).  A work item is (list l,
 // up to G pairs): the G LUTs are interleaved per entry ([m][j][g]) so one
 // ds_read_b{32,64,128} returns the G lookups of a code and the bank conflicts
 // of the random 8-bit gathers are paid once per G lookups.
@@ -1861,13 +1911,15 @@ __device__ __forceinline__ int div_small(int x, int d, float inv_d) {
 
 // ---- fused planning: the list scan derives its work items itself
 // (pl.fused: nloc <= kFusedPlanLists and fewer than 65536 items).  Every
-// workgroup forms the exclusive prefix of the per-list item counts
-// ceil(min(cnt, cap) / G) of both kinds in scheduling order (pl.order) in LDS;
-// item e of kind 0 ([0, N0)) or kind 1 ([N0, N)) is then found by a two-step
-// search over that prefix, and its record words are loaded from the counts,
-// list offsets and bucket in one round trip.  Replaces k_plan_items (one
-// launch) for the shard sizes where it fits in LDS.
+// workgroup forms the exclusive prefix of the per-list lead and rest item
+// counts (list_items) in scheduling order (pl.order) in LDS; lead item e
+// ([0, N0)) or rest item e ([N0, N)) is then found by a two-step search over
+// that prefix, and its record words are loaded from the counts, list offsets
+// and bucket in one round trip.  Replaces k_plan_items (one launch) for the
+// shard sizes where it fits in LDS.
 constexpr int kFusedPlanLists = 1024;
+constexpr int kOrdFillShift = 10;  // s_ord[j] = list rank | free entries << 10 | filled << 12 (list_items)
+static_assert(kFusedPlanLists <= (1 << kOrdFillShift), "the list rank and the fill bits share 16 bits");
 
 // returns (N0, N1); ws: >= 8 ints of scratch (LDS)
 __device__ __forceinline__ int2 fused_plan_prefix(const ListPlan& pl, int nloc, int G, uint16_t* ex0, uint16_t* ex1,
@@ -1879,9 +1931,12 @@ __device__ __forceinline__ int2 fused_plan_prefix(const ListPlan& pl, int nloc, 
   for (int u = 0; u < 4; u++) {
     const int j = 4 * tid + u;
     const int jl = j < nloc ? (pl.order ? pl.order[j] : j) : 0;
-    a[u] = j < nloc ? (min(pl.cnt[jl], pl.cap) + G - 1) / G : 0;
-    b[u] = j < nloc ? (min(pl.cnt[nloc + jl], pl.cap) + G - 1) / G : 0;
-    if (j < nloc) ord[j] = (uint16_t)jl;
+    const ListItems li = list_items(pl.cnt[jl], pl.cnt[nloc + jl], pl.cap, G);
+    a[u] = j < nloc ? li.lead : 0;
+    b[u] = j < nloc ? li.rest : 0;
+    // the list's free entries (< G <= 4) and whether they are filled ride in the bits above
+    // its rank (< 1024): fused_record needs them before any of the record's loads has returned
+    if (j < nloc) ord[j] = (uint16_t)(jl | (li.free << kOrdFillShift) | (li.filled << (kOrdFillShift + 2)));
     sa += a[u];
     sb += b[u];
   }
@@ -1924,15 +1979,15 @@ __device__ __forceinline__ int2 fused_plan_prefix(const ListPlan& pl, int nloc, 
 // Item e's record, fetched ahead: lane w (< 16) issues ONE unconditional load of
 // record word w -- no divergent branches, so no register receives loads under
 // different exec masks -- whose value nothing consumes until unpack (the load stays
-// in flight during the current item's scan).  Fused planning: word 1 = the list's
-// pair count (count = min(G, min(c, cap) - t G)), words 2 / 3 = the low words of
-// off[l + 1] / off[l] (n = w2 - w3), word 4 = off[l]'s high word, words 5..8 / 9..12
-// = the bucket's pair ids / dis0 bits; the list, kind and t are wave-uniform and
-// kept in scalars (the other lanes load word 1 again).  Non-fused: the 16 words of
-// pl.recs (write_item's layout).
+// in flight during the current item's scan).  Fused planning: word 1 = a pair count
+// c of the list (the item's count = min(G, min(c, cap) - off)), words 2 / 3 = the low
+// words of off[l + 1] / off[l] (n = w2 - w3), word 4 = off[l]'s high word, words 5..8 /
+// 9..12 = the buckets' pair ids / dis0 bits; the list, kind (0 lead, 1 rest) and off
+// are wave-uniform and kept in scalars (the other lanes load word 1 again).
+// Non-fused: the 16 words of pl.recs (write_item's layout).
 struct Rec {
   int raw;  // this lane's loaded word (in flight)
-  int l, kind, t;
+  int l, kind, off;
 };
 __device__ __forceinline__ Rec fused_record(const ScanArgs& a, const ListPlan& pl, int nloc, int e, int n0,
                                            const uint16_t* ex0, const uint16_t* ex1, const uint16_t* ord, int G,
@@ -1946,23 +2001,42 @@ __device__ __forceinline__ Rec fused_record(const ScanArgs& a, const ListPlan& p
   const int j0 = 16 * (63 - __builtin_clzll(m1));
   const uint64_t m2 = __builtin_amdgcn_ballot_w64(lane < 16 && j0 + lane < nloc && (int)ex[j0 + lane] <= ek);
   const int j = j0 + 63 - __builtin_clzll(m2);
-  const int jl = __builtin_amdgcn_readfirstlane((int)ord[j]);
-  const int t = ek - __builtin_amdgcn_readfirstlane((int)ex[j]);
+  const int ow = __builtin_amdgcn_readfirstlane((int)ord[j]);
+  const int jl = ow & ((1 << kOrdFillShift) - 1);
+  const int filled = ow >> (kOrdFillShift + 2), f = filled ? (ow >> kOrdFillShift) & 3 : 0;
+  const int exj = __builtin_amdgcn_readfirstlane((int)ex[j]);
+  const int t = ek - exj;
+  // Entry s = t G + g of a lead item is kind-0 slot s below c0 and kind-1 slot s - c0 from
+  // there on; of a rest item, kind-1 slot s + f.  c0 = L G - (free entries) comes from the
+  // LDS prefix and s_ord, so no address waits for a count: the record stays one round
+  // trip.  The one count word of a filled list is the kind-1 count c1 for both
+  // populations (lead item t holds min(G, c1 + c0 - t G) pairs, rest item t
+  // min(G, c1 - f - t G)); of a list that is not filled, the count of the item's own kind
+  // (its lead items' entries from c0 on are absent pairs, their slots read and ignored).
+  int c0 = 0x3fffffff, off = t * G + f;
+  if (!kind) {
+    c0 = (__builtin_amdgcn_readfirstlane((int)ex[j + 1]) - exj) * G - ((ow >> kOrdFillShift) & 3);
+    off = filled ? t * G - c0 : t * G;
+  }
+  const int cw = kind | filled;
   const int64_t l = a.list_lo + jl;
   const int* off32 = reinterpret_cast<const int*>(a.list_off);
   const int* bk32 = reinterpret_cast<const int*>(pl.bucket);
   const int w = lane & 15;
-  const int64_t slot = ((int64_t)jl * 2 + kind) * pl.cap + min(t * G + ((w - 5) & 3), pl.cap - 1);
+  const int s = t * G + ((w - 5) & 3);
+  const int bk = kind | (s >= c0 ? 1 : 0);
+  const int ix = kind ? s + f : s >= c0 ? s - c0 : s;
+  const int64_t slot = ((int64_t)jl * 2 + bk) * pl.cap + min(ix, pl.cap - 1);
   const int* src = w == 2 ? off32 + 2 * (l + 1)
                  : w == 3 ? off32 + 2 * l
                  : w == 4 ? off32 + 2 * l + 1
                  : (w >= 5 && w <= 12) ? bk32 + 2 * slot + (w <= 8 ? 0 : 1)
-                 : pl.cnt + kind * nloc + jl;  // word 1 (and the unused lanes)
+                 : pl.cnt + cw * nloc + jl;  // word 1 (and the unused lanes)
   Rec r;
   r.raw = *src;
   r.l = (int)l;
   r.kind = kind;
-  r.t = t;
+  r.off = off;
   return r;
 }
 
@@ -2036,7 +2110,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
     if (!pl.fused) {
       Rec r;
       r.raw = pl.recs[(int64_t)idx * 16 + (lane & 15)];
-      r.l = r.kind = r.t = 0;  // (words 0, 13 of the raw record)
+      r.l = r.kind = r.off = 0;  // (words 0, 13 of the raw record)
       return r;
     }
     return fused_record(a, pl, nloc, idx, n_items0, s_ex[0], s_ex[1], s_ord, G, lane);
@@ -2046,7 +2120,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
     if (pl.fused) {  // raw words (fused_record)
       it.l = rc.l;
       it.kind = rc.kind;
-      it.cnt = min(G, min(__builtin_amdgcn_readlane(rv, 1), pl.cap) - rc.t * G);
+      it.cnt = min(G, min(__builtin_amdgcn_readlane(rv, 1), pl.cap) - rc.off);
       it.n = __builtin_amdgcn_readlane(rv, 2) - __builtin_amdgcn_readlane(rv, 3);
     } else {
       it.l = __builtin_amdgcn_readlane(rv, 0);
@@ -2081,6 +2155,10 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
   if (tid == 0) {
     const int t = atomicAdd(pl.hdr + 2, 1);
     s_next = t < n_items ? t : -1;
+    if (pl.fused && t == 0) {  // the item counts k_plan_items would have left (read by tests and tools)
+      pl.hdr[0] = n_items;
+      pl.hdr[1] = n_items0;
+    }
   }
   __syncthreads();
   int cur = s_next;
@@ -2691,7 +2769,7 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
     const int rv = rc.raw;
     it.l = rc.l;
     it.kind = rc.kind;
-    it.cnt = min(G, min(__builtin_amdgcn_readlane(rv, 1), pl.cap) - rc.t * G);
+    it.cnt = min(G, min(__builtin_amdgcn_readlane(rv, 1), pl.cap) - rc.off);
     it.n = __builtin_amdgcn_readlane(rv, 2) - __builtin_amdgcn_readlane(rv, 3);
     it.beg = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(rv, 4) << 32) |
                        (uint32_t)__builtin_amdgcn_readlane(rv, 3));
@@ -2724,6 +2802,10 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
   if (tid == 0) {
     const int t = atomicAdd(pl.hdr + 2, 1);
     s_next = t < n_items ? t : -1;
+    if (t == 0) {  // the item counts k_plan_items would have left (read by tests and tools)
+      pl.hdr[0] = n_items;
+      pl.hdr[1] = n_items0;
+    }
   }
   __syncthreads();
   int cur = s_next;
@@ -4348,7 +4430,9 @@ int list_scan_group(int M, int k) {
 }
 
 int list_scan_max_items(int64_t npairs, int nloc, int G) {
-  // sum over (list, kind) buckets of ceil(c / G) <= npairs / G + (non-empty buckets)
+  // sum over (list, kind) buckets of ceil(c / G) <= npairs / G + (non-empty buckets);
+  // a list whose lead item takes kind-1 pairs has ceil((c0 + c1) / G) <= ceil(c0 / G) +
+  // ceil(c1 / G) items, so the bound holds for either composition (list_items)
   const int64_t v = (npairs + G - 1) / G + std::min<int64_t>(2 * (int64_t)nloc, npairs) + 8;
   return (int)v;
 }

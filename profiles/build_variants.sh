@@ -4,11 +4,12 @@
 # Without arguments: the variants that are kept in the tree behind a macro, so that they are compiled somewhere:
 #   fourpass  -DSCAN_LEAN_PASSES=4  (four-pass k_scan_lean, profiles/scan_four_pass.md)
 #   onepass   -DSCAN_LEAN_SPLIT=0   (one-pass k_scan_lean, profiles/scan_split_lut.md)
+#   nofill    -DPLAN_FILL_LEAD=0    (work items of one kind only, profiles/plan_fill_lead.md)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/chameleon-rag-acceleration_amd/csrc
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I$R/include -I$C"
-[ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0"
+[ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0" "nofill:-DPLAN_FILL_LEAD=0"
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   O=$R/chameleon-rag-acceleration_amd/lib/var/$name

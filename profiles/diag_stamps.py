@@ -2,7 +2,7 @@
 
 Slots per (workgroup, iteration), thread 0: 0 item start (barrier A), 1 LUT
 built (barrier B), 2 scan done, 3 partial writes done, 4 codes, 5 pairs |
-kind << 8, 6 wave 0's cycles in the super-batch gathers, 7 its admitted
+(0 lead / 1 rest item) << 8, 6 wave 0's cycles in the super-batch gathers, 7 its admitted
 candidates | drains << 32.
 
 Usage (on the GPU box):
@@ -11,8 +11,10 @@ Usage (on the GPU box):
 
 Builds the C2 index (bench.py's workload), runs a few warm-up searches, then one
 stamped search, and prints per phase (LUT build incl. its loads, scan, partial
-writes) the cycle statistics split by item kind (0 = first probe, 1 = other),
-the admitted-candidate counts (wave 0) and the per-workgroup busy fraction.
+writes) the cycle statistics split by item population (lead = the items that hold
+the queries' first probes, filled up with the list's other pairs unless the build has
+-DPLAN_FILL_LEAD=0; rest = every other item), the pairs per item, the admitted-candidate
+counts (wave 0) and the per-workgroup busy fraction.
 """
 import ctypes
 import os
@@ -57,13 +59,14 @@ def main():
     t0, t1, t2, t3, n, ck, push, tau = [a[:, :, i] for i in range(8)]
     kind = (ck >> 8) & 1
     cnt = ck & 0xFF
-    print(f"items {valid.sum()} (kind0 {(valid & (kind == 0)).sum()}, kind1 {(valid & (kind == 1)).sum()}); "
+    print(f"items {valid.sum()} (lead {(valid & (kind == 0)).sum()}, rest {(valid & (kind == 1)).sum()}); "
+          f"pairs {cnt[valid].sum()} (lead {cnt[valid & (kind == 0)].sum()}, rest {cnt[valid & (kind == 1)].sum()}); "
           f"per-WG mean {valid.sum(1)[valid.any(1)].mean():.1f} max {valid.sum(1).max()}")
-    for kname, sel in (("kind0", valid & (kind == 0)), ("kind1", valid & (kind == 1)), ("all", valid)):
+    for kname, sel in (("lead", valid & (kind == 0)), ("rest", valid & (kind == 1)), ("all", valid)):
         if not sel.any():
             continue
         print(f"-- {kname}: codes/item {n[sel].mean():.0f}, pairs/item {cnt[sel].mean():.2f}, "
-              f"admitted (wave 0, all pairs) {(tau[sel] & 0xFFFFFFFF).mean():.1f}, drains {(tau[sel] >> 32).mean():.2f}, "
+              f"admitted per wave and item (wave 0, all pairs) {(tau[sel] & 0xFFFFFFFF).mean():.1f}, drains {(tau[sel] >> 32).mean():.2f}, "
               f"gather cycles (wave 0) {push[sel].mean():.0f}")
         d_loose, d_admit, d_fdrain, t_loop = (a[:, :, i][sel] for i in (8, 9, 10, 11))
         print(f"   scan phase (wave 0): setup {(t_loop - t1[sel]).mean():.0f}, gathers {push[sel].mean():.0f}, "
@@ -83,11 +86,11 @@ def main():
           f"kernel span {gend - g0} cycles")
     print(f"WG start offset p50 {np.median(first[act] - g0):.0f} max {(first[act] - g0).max():.0f}; "
           f"WG end offset p10 {np.percentile(last[act] - g0, 10):.0f} p50 {np.median(last[act] - g0):.0f}")
-    # kind-1 items started before (within the kernel) vs after all kind-0 items ended
+    # rest items started before (within the kernel) vs after all lead items ended
     k0_end = np.where(valid & (kind == 0), t3, 0).max()
     k1 = valid & (kind == 1)
     early = k1 & (t0 < k0_end)
-    print(f"kind-1 items started before the last kind-0 item ended: {early.sum()} of {k1.sum()}; "
+    print(f"rest items started before the last lead item ended: {early.sum()} of {k1.sum()}; "
           f"their scan mean {(t2 - t1)[early].mean() if early.any() else 0:.0f} vs later "
           f"{(t2 - t1)[k1 & ~early].mean() if (k1 & ~early).any() else 0:.0f}")
 

@@ -1780,6 +1780,18 @@ int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n,
 // live in one device image that grows geometrically; the label of a code is its
 // position.  Device calls on different streams are ordered one after the other
 // (one workspace per handle).
+namespace {
+
+// queries per chunk of a flat-PQ search: the tables (M KiB per query) within kChunkBytes,
+// the grid's y extent (shared by the handle and ivfpq_pq_debug_plan)
+int64_t pq_query_chunk(int M, int64_t n) {
+  return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
+}
+
+const char* pq_supported_M_text() { return " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)"; }
+
+}  // namespace
+
 struct ivfpq_pq_index {
   int d = 0, M = 0, nbits = 8, ksub = 256, metric = IVFPQ_METRIC_L2, device = 0;
   bool trained = false;
@@ -1863,10 +1875,7 @@ struct ivfpq_pq_index {
     }
   }
 
-  // queries per chunk: the tables (M KiB per query) within kChunkBytes, the grid's y extent
-  int64_t query_chunk(int64_t n) const {
-    return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
-  }
+  int64_t query_chunk(int64_t n) const { return pq_query_chunk(M, n); }
 
   // c device-resident queries -> D, I (device), all on s
   void search_chunk(const float* xd, int64_t c, int k, float* D, int64_t* I, hipStream_t s) {
@@ -1936,8 +1945,7 @@ int ivfpq_pq_create(int d, int M, int nbits, int metric, int device, ivfpq_pq_in
     require(d > 0 && M > 0, "d and M must be positive");
     require(d % M == 0, "d must be a multiple of M");
     require(nbits == 8, "only nbits=8 is supported");
-    require(pq_flat_supported_M(M),
-            "M=" + std::to_string(M) + " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)");
+    require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
     require(d <= 2048, "d > 2048 not supported");
     require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
     int ndev = 0;
@@ -2110,6 +2118,24 @@ int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out) {
     HIPCHECK(hipMemcpyAsync(out, h->d_codes.as<uint8_t>() + i0 * h->M, (size_t)n * h->M, hipMemcpyDeviceToHost,
                             h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
+  });
+}
+
+// Test hook (ivfpq_test.h): host arithmetic only, no handle and no device call.
+int ivfpq_pq_debug_plan(int M, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
+                        int64_t* query_chunk) {
+  return guarded([&] {
+    require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(nq >= 1, "query count must be positive");
+    require(nb >= 1 && nb < (int64_t)INT32_MAX, "IndexPQ holds at most 2^31 - 2 codes");
+    const int64_t qc = pq_query_chunk(M, nq);
+    const PqScanPlan pl = pq_scan_plan(M, k, std::min(nq, qc), nb);
+    if (G) *G = pl.G;
+    if (ranges) *ranges = pl.ranges;
+    if (rows) *rows = pl.rows;
+    if (S) *S = pl.S;
+    if (query_chunk) *query_chunk = qc;
   });
 }
 

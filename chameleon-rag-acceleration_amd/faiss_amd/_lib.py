@@ -23,7 +23,7 @@ c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_handle = ctypes.c_void_p
 
-# name -> (restype, argtypes); mirrors include/ivfpq.h one to one, plus the three
+# name -> (restype, argtypes); mirrors include/ivfpq.h one to one, plus the
 # test hooks of include/ivfpq_test.h (used only by tests/).
 SIGNATURES = {
     "ivfpq_last_error": (ctypes.c_char_p, []),
@@ -110,6 +110,9 @@ SIGNATURES = {
     "ivfpq_pq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 4),
     "ivfpq_pq_get_codebook": (ctypes.c_int, [c_handle, c_f32p]),
     "ivfpq_pq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
+    "ivfpq_pq_debug_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), c_i64p,
+                                           ctypes.POINTER(ctypes.c_int), c_i64p]),
 }
 
 

@@ -5,7 +5,8 @@
  * these, and a production caller has no reason to use them.  They exist so that the
  * test suite can drive the repair path of the probe merge (tests/test_gpu_repair.py),
  * check the bounded scan against seeded bounds ("Uniform
- * bounds") and inspect a workspace after a search.  None of them is reachable through
+ * bounds"), inspect a workspace after a search and ask how a flat-PQ search is split
+ * (tests/test_gpu_indexpq_paths.py).  None of them is reachable through
  * the faiss_amd surface used by the reference's callers.
  */
 #ifndef CHAMELEON_IVFPQ_TEST_H
@@ -30,6 +31,15 @@ int ivfpq_debug_workspace(ivfpq_index* h, int ws, int what, void* dst, int64_t c
  * starts with query i's shared bound tau_i = keys[i] instead of +inf (one-shot).  Any
  * keys[i] >= that query's true k-th key is a valid bound, and results must not change. */
 int ivfpq_debug_seed_tau(ivfpq_index* h, int64_t n, const float* keys);
+/* How a flat-PQ (IndexPQ) search of nq queries over nb codes is split, so that a test can
+ * assert the path it claims to reach: query_chunk = the queries per chunk an ivfpq_pq_index
+ * of this M takes at a time, and for a chunk of min(nq, query_chunk) queries G = queries per
+ * scan workgroup, ranges x rows = the code ranges (rows a multiple of 2048; a workgroup
+ * passes over its range 2048 rows at a time at k <= 64, 1024 above), S = 4 * ranges = the
+ * sorted partial lists per query that the merge takes.  Host arithmetic only: no handle, no
+ * device call.  Unsupported M or k is an error.  Null outputs are skipped. */
+int ivfpq_pq_debug_plan(int M, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
+                        int64_t* query_chunk);
 
 #ifdef __cplusplus
 }

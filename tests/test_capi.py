@@ -31,10 +31,11 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_test_hooks_are_not_in_the_drop_in_header():
-    """Fault injection, seeded bounds and workspace dumps are test hooks (ivfpq_test.h),
-    not part of the Faiss-replacing boundary."""
+    """Fault injection, seeded bounds, workspace dumps and the flat-PQ scan plan are test
+    hooks (ivfpq_test.h), not part of the Faiss-replacing boundary."""
     hooks = declared_functions(TEST_HEADER)
-    assert sorted(hooks) == ["ivfpq_debug_seed_tau", "ivfpq_debug_workspace", "ivfpq_set_fault_injection"]
+    assert sorted(hooks) == ["ivfpq_debug_seed_tau", "ivfpq_debug_workspace", "ivfpq_pq_debug_plan",
+                             "ivfpq_set_fault_injection"]
     assert not set(hooks) & set(declared_functions())
 
 

@@ -13,7 +13,10 @@ Quantizers are installed with ``set_trained`` from a seeded random codebook, exc
 the training test.  Code ranges: a batch is split into ranges of a multiple of 2048 rows
 (``kPqTileRows`` in csrc/pq_flat.h), at most 12288 / (4 k) of them (``pq_scan_plan``);
 NB_RANGES = 2 * 2048 + 777 gives three ranges with a ragged last one at every (nq, k)
-used here, k = 1024 included.
+used here, k = 1024 included.  Each of those ranges is 2048 rows, which at k <= 64 is a
+single pass of a scan workgroup (two passes of 1024 rows above): the scan loop over several
+passes at k <= 64, the other table widths and blockings, the k and nb boundaries and the
+candidate queue's worst case are in tests/test_gpu_indexpq_paths.py.
 """
 import functools
 

@@ -13,7 +13,7 @@ from faiss_amd import index as fidx
 PQ_SYMBOLS = ["ivfpq_pq_create", "ivfpq_pq_free", "ivfpq_pq_train", "ivfpq_pq_set_trained", "ivfpq_pq_add",
               "ivfpq_pq_add_device", "ivfpq_pq_add_codes", "ivfpq_pq_reset", "ivfpq_pq_search",
               "ivfpq_pq_search_device", "ivfpq_pq_ntotal", "ivfpq_pq_is_trained", "ivfpq_pq_get_dims",
-              "ivfpq_pq_get_codebook", "ivfpq_pq_get_codes"]
+              "ivfpq_pq_get_codebook", "ivfpq_pq_get_codes", "ivfpq_pq_debug_plan"]
 
 
 def test_symbols_exported_and_bound():
@@ -43,6 +43,84 @@ def test_null_handle_is_an_error_not_a_crash():
     assert lib.ivfpq_pq_is_trained(None) == 0
     assert lib.ivfpq_pq_reset(None) != 0
     assert lib.ivfpq_pq_free(None) == 0
+
+
+# (M, k, nq, nb) -> (ranges, rows, S, query chunk), worked out by hand from pq_scan_plan:
+#   groups = ceil(min(nq, chunk) / 4), tiles = ceil(nb / 2048),
+#   r = min(ceil(1024 / groups), max(1, 12288 // (4 k)), tiles), rows = ceil(tiles / r) * 2048,
+#   ranges = ceil(nb / rows), S = 4 ranges; chunk = min(nq, 256 MiB / (M KiB), 4096)
+PLANS = [
+    ((8, 10, 5, 4873), (3, 2048, 12, 5)),            # 2 groups: min(512, 307, 3 tiles)
+    ((8, 10, 4, 4873), (3, 2048, 12, 4)),            # the tail chunk of 4100 queries
+    ((8, 1, 4100, 4873), (1, 6144, 4, 4096)),        # 1024 groups: one range of all 3 tiles
+    ((8, 64, 2049, 4873), (2, 4096, 8, 2049)),       # 513 groups: ceil(1024 / 513) = 2
+    ((128, 10, 4100, 4873), (2, 4096, 8, 2048)),     # 128 KiB of table per query: chunk 2048, 512 groups
+    ((8, 10, 5, 67589), (34, 2048, 136, 5)),         # 34 tiles < 307
+    ((8, 64, 5, 67589), (34, 2048, 136, 5)),         # 34 tiles < 48
+    ((8, 96, 5, 67589), (17, 4096, 68, 5)),          # 12288 // 384 = 32 -> 2 tiles each -> 17 ranges
+    ((8, 256, 1, 49152), (12, 4096, 48, 1)),         # 12288 // 1024 = 12, 24 tiles
+    ((8, 257, 1, 49152), (8, 6144, 32, 1)),          # 12288 // 1028 = 11 -> 3 tiles each -> 8 ranges
+    ((8, 1000, 1, 18432), (3, 6144, 12, 1)),         # 12288 // 4000 = 3, 9 tiles
+    ((16, 1024, 37, 1), (1, 2048, 4, 37)),           # one row
+]
+
+
+@pytest.mark.parametrize("args,want", PLANS, ids=["-".join(map(str, a)) for a, _ in PLANS])
+def test_debug_plan_values(args, want):
+    from indexpq_ref import plan
+
+    p = plan(*args)
+    assert (p.ranges, p.rows, p.S, p.chunk) == want
+    assert p.G == 4
+
+
+@pytest.mark.parametrize("args,word", [((24, 10, 5, 100), "8, 16, 32, 48, 64"), ((144, 10, 5, 100), "not supported"),
+                                       ((8, 0, 5, 100), "k must be in"), ((8, 1025, 5, 100), "k must be in")])
+def test_debug_plan_rejects_unsupported_shapes(args, word):
+    lib = _lib.load()
+    assert lib.ivfpq_pq_debug_plan(*args, None, None, None, None, None) != 0
+    assert word in lib.ivfpq_last_error().decode()
+    assert lib.ivfpq_pq_debug_plan(8, 10, 5, 100, None, None, None, None, None) == 0  # null outputs are skipped
+
+
+@pytest.mark.parametrize("kind", [0, 1], ids=["ip", "l2"])
+def test_vectorised_tree_equals_the_oracle_bit_for_bit(kind):
+    from indexpq_ref import tree_np
+    from oracle import oracle as O
+
+    rng = np.random.default_rng(17)
+    for d in list(range(1, 34)) + [48, 100, 256]:
+        x = rng.standard_normal((3, d)).astype(np.float32)
+        y = (rng.standard_normal((5, d)) * 3).astype(np.float32)
+        got = tree_np(x[:, None, :], y[None], kind)
+        assert got.dtype == np.float32 and got.shape == (3, 5)
+        want = np.array([[O.tree(x[i], y[j], kind) for j in range(5)] for i in range(3)], np.float32)
+        assert got.tobytes() == want.tobytes(), d
+
+
+def test_shared_reference_sums_and_order():
+    """indexpq_ref's sums and top-k against the plain statements of the same thing."""
+    import indexpq_ref as R
+
+    rng = np.random.default_rng(18)
+    nq, M, nb = 7, 16, 90
+    tab = rng.standard_normal((nq, M, 256)).astype(np.float32)
+    codes = rng.integers(0, 4, (nb, M), dtype=np.uint8)  # few distinct codes: ties
+    codes[40:] = codes[:50]
+    want = np.zeros((nq, nb), np.float32)
+    for m in range(M):
+        want += tab[:, m, codes[:, m]]
+    acc = R.ref_sums(tab, codes)
+    assert acc.tobytes() == want.tobytes()
+    for metric in (R.L2, R.IP):
+        for k in (1, 10, 90, 100):
+            D, I = R.ref_topk(acc, k, metric, R.ref_order(acc, 100, metric))
+            for q in range(nq):
+                order = np.lexsort((np.arange(nb), -acc[q] if metric == R.IP else acc[q]))[:k]
+                np.testing.assert_array_equal(I[q, :len(order)], order)
+                np.testing.assert_array_equal(D[q, :len(order)], acc[q][order])
+                assert (I[q, len(order):] == -1).all()
+                assert (D[q, len(order):] == (-R.FMAX if metric == R.IP else R.FMAX)).all()
 
 
 def test_ixpq_layout_and_round_trip():

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -29,6 +30,7 @@
 #include "ivfpq_kernels.h"
 #include "ivfpq_build.h"
 #include "pq_flat.h"
+#include "ivf_flat.h"
 
 using namespace chivf;
 
@@ -2136,6 +2138,546 @@ int ivfpq_pq_debug_plan(int M, int k, int64_t nq, int64_t nb, int* G, int* range
     if (rows) *rows = pl.rows;
     if (S) *S = pl.S;
     if (query_chunk) *query_chunk = qc;
+  });
+}
+
+}  // extern "C"
+
+// ============================================================ IVF-Flat (IndexIVFFlat)
+// faiss.IndexIVFFlat: the IVF-PQ handle's coarse quantizer (k-means, matrix-core keys,
+// top-nprobe selection) over inverted lists of the raw fp32 vectors, scanned by
+// ivf_flat.hip.  The vectors live only in the device image {list_off, vectors, ids},
+// every list sorted by label; adds wait in a pending set on the device and are merged
+// with the image kernels of ivfpq_build.h at code size 4 d.  Device calls on different
+// streams are ordered one after the other (one workspace per handle).
+struct ivfpq_ivfflat_index {
+  int d = 0, nlist = 0, metric = IVFPQ_METRIC_L2, device = 0;
+  int nprobe = 1;
+  bool trained = false;
+  std::vector<float> centroids;  // [nlist][d]
+  // the coarse quantizer: an IVF-PQ handle that holds only the centroids' device copies,
+  // its stream and the k-means / coarse workspaces
+  ivfpq_index base;
+  int64_t ntotal = 0, next_id = 0;
+  int64_t img_n = 0;  // vectors in the image (ntotal = img_n + q_n)
+  DevBuf d_vecs, d_ids, d_off;
+  std::vector<int64_t> h_off;      // the image's list offsets
+  std::vector<int64_t> range_top;  // range_top[p] = row ranges of the p longest lists (the slot bound)
+  DevBuf q_lists, q_ids, q_x;      // pending adds: list numbers, labels, vectors
+  int64_t q_n = 0, q_cap = 0;
+  DevBuf w_D, w_x, h_D, h_I, h_Iq;  // add scratch; staging of the host entry points
+  DevBuf w_lists, w_dis, p_cnt, p_bucket, p_items, p_used, p_tau, p_partD, p_partI, p_tmpD, p_tmpI;
+  hipStream_t stream = nullptr;  // = base.stream
+  hipEvent_t done = nullptr;     // recorded after every device call, on done_stream
+  hipStream_t done_stream = nullptr;
+  bool done_pending = false;
+  std::mutex mu;
+
+  ~ivfpq_ivfflat_index() {
+    if (done) (void)hipEventDestroy(done);
+  }
+  bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
+  size_t row_bytes() const { return sizeof(float) * (size_t)d; }
+
+  void order_after(hipStream_t s) {
+    if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
+  }
+  void mark_done(hipStream_t s) {
+    HIPCHECK(hipEventRecord(done, s));
+    done_stream = s;
+    done_pending = true;
+  }
+  void quiesce() {
+    if (done_pending) HIPCHECK(hipEventSynchronize(done));
+    done_pending = false;
+  }
+
+  // the centroids' device copies of ivfpq_index::upload_trained (no codebook, no T1)
+  void upload_centroids() {
+    quiesce();
+    base.d_cent.ensure(sizeof(float) * nlist * d);
+    base.d_cnorm.ensure(sizeof(float) * nlist);
+    HIPCHECK(hipMemcpyAsync(base.d_cent.p, centroids.data(), sizeof(float) * nlist * d, hipMemcpyHostToDevice, stream));
+    launch_row_norms(base.d_cent.as<float>(), nlist, d, base.d_cnorm.as<float>(), stream);
+    const int ldc = (nlist + 3) & ~3;
+    std::vector<float> ct((size_t)ldc * d, 0.f);
+    for (int l = 0; l < nlist; l++)
+      for (int t = 0; t < d; t++) ct[(size_t)t * ldc + l] = centroids[(size_t)l * d + t];
+    base.d_centT.ensure(sizeof(float) * ct.size());
+    HIPCHECK(hipMemcpyAsync(base.d_centT.p, ct.data(), sizeof(float) * ct.size(), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(stream));
+    trained = true;
+  }
+
+  void set_offsets(std::vector<int64_t> off) {
+    h_off = std::move(off);
+    std::vector<int64_t> r(nlist);
+    for (int l = 0; l < nlist; l++) r[l] = (h_off[l + 1] - h_off[l] + kIvfFlatRangeRows - 1) / kIvfFlatRangeRows;
+    std::sort(r.begin(), r.end(), std::greater<int64_t>());
+    range_top.assign(nlist + 1, 0);
+    for (int l = 0; l < nlist; l++) range_top[l + 1] = range_top[l] + r[l];
+  }
+
+  // an empty image (create, reset)
+  void clear_image() {
+    quiesce();
+    q_lists.release();
+    q_ids.release();
+    q_x.release();
+    q_n = q_cap = 0;
+    d_vecs.release();
+    d_ids.release();
+    d_off.ensure(sizeof(int64_t) * (nlist + 1));
+    HIPCHECK(hipMemsetAsync(d_off.p, 0, sizeof(int64_t) * (nlist + 1), stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    set_offsets(std::vector<int64_t>(nlist + 1, 0));
+    img_n = ntotal = next_id = 0;
+  }
+
+  void pend_reserve(int64_t need, hipStream_t s) {
+    if (need <= q_cap) return;
+    const int64_t cap = std::max<int64_t>(need, q_cap * 2);
+    DevBuf l2, i2, x2;
+    l2.ensure(sizeof(int64_t) * cap);
+    i2.ensure(sizeof(int64_t) * cap);
+    x2.ensure(row_bytes() * cap);
+    if (q_n > 0) {
+      HIPCHECK(hipMemcpyAsync(l2.p, q_lists.p, sizeof(int64_t) * q_n, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(i2.p, q_ids.p, sizeof(int64_t) * q_n, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(x2.p, q_x.p, row_bytes() * q_n, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipStreamSynchronize(s));
+    }
+    std::swap(q_lists.p, l2.p);
+    std::swap(q_lists.bytes, l2.bytes);
+    std::swap(q_ids.p, i2.p);
+    std::swap(q_ids.bytes, i2.bytes);
+    std::swap(q_x.p, x2.p);
+    std::swap(q_x.bytes, x2.bytes);
+    q_cap = cap;
+  }
+
+  // n vectors (host or device) into the pending set: copied behind it, then assigned
+  // there by the search's coarse kernels (top-1), as ivfpq_index::add_dev assigns.
+  // Merged into the image before the lists are next read, or once the pending set is
+  // as large as the image (and at least kChunkBytes), so that a sequence of adds
+  // moves every vector O(1) times.
+  void add_dev(int64_t n, const float* x, bool x_on_device, const int64_t* ids, bool ids_on_device, hipStream_t s) {
+    require(trained, "index is not trained");
+    if (n <= 0) return;
+    require(ntotal + n < (int64_t)INT32_MAX, "IndexIVFFlat holds fewer than 2^31 - 1 vectors");
+    order_after(s);
+    quiesce();
+    const int64_t rows = nlist >= kSegmentedNlist ? std::min<int64_t>(n, 1 << 18)
+                                                  : std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / ((size_t)nlist * 4)));
+    pend_reserve(q_n + n, s);
+    float* xd = q_x.as<float>() + q_n * d;
+    int64_t* lists = q_lists.as<int64_t>() + q_n;
+    HIPCHECK(hipMemcpyAsync(xd, x, row_bytes() * n, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    w_D.ensure(sizeof(float) * rows);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t c = std::min(rows, n - r0);
+      base.coarse_launch(xd + r0 * d, c, 1, w_D.as<float>(), lists + r0, s);
+      HIPCHECK(hipGetLastError());
+    }
+    if (!ids) {
+      launch_iota_i64(q_ids.as<int64_t>() + q_n, n, next_id, s);
+      next_id += n;
+    } else {
+      HIPCHECK(hipMemcpyAsync(q_ids.as<int64_t>() + q_n, ids, sizeof(int64_t) * n,
+                              ids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    q_n += n;
+    ntotal += n;
+    if (q_n >= std::max<int64_t>(img_n, (int64_t)(kChunkBytes / row_bytes()))) flush_pending(s);
+  }
+
+  // The pending vectors merged into the image: sorted by (list, label) alone, then
+  // interleaved list by list into the label-sorted image (ivfpq_index::flush_pending
+  // with the vector's 4 d bytes as the code).
+  void flush_pending(hipStream_t s) {
+    if (q_n == 0) return;
+    quiesce();
+    ImageMergeArgs g;
+    g.nlist = nlist;
+    g.lo = 0;
+    g.hi = nlist;
+    g.M = (int)row_bytes();
+    g.n_old = 0;
+    g.n_new = q_n;
+    g.new_lists = q_lists.as<int64_t>();
+    g.new_ids = q_ids.as<int64_t>();
+    g.new_codes = q_x.as<uint8_t>();
+    DevBuf new_off, out_off, scratch, vecs_n, ids_n;
+    new_off.ensure(sizeof(int64_t) * (nlist + 1));
+    g.off_out = new_off.as<int64_t>();
+    const size_t sb = image_merge_scratch_bytes(q_n, nlist);
+    scratch.ensure(sb);
+    HIPCHECK(image_merge_sort(g, scratch.p, sb, s));
+    std::vector<int64_t> noff(nlist + 1);
+    HIPCHECK(hipMemcpyAsync(noff.data(), new_off.p, sizeof(int64_t) * (nlist + 1), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    require(noff[nlist] == q_n, "pending merge: a vector was assigned to no list");
+    vecs_n.ensure(std::max<size_t>(16, row_bytes() * q_n));
+    ids_n.ensure(std::max<size_t>(16, sizeof(int64_t) * q_n));
+    g.codes_out = vecs_n.as<uint8_t>();
+    g.ids_out = ids_n.as<int64_t>();
+    HIPCHECK(image_merge_gather(g, q_n, scratch.p, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    scratch.release();
+    q_x.release();  // (gathered: the pending vectors now live in vecs_n)
+    std::vector<int64_t> off(nlist + 1);
+    int64_t mx = 0;
+    for (int l = 0; l <= nlist; l++) {
+      off[l] = h_off[l] + noff[l];
+      if (l < nlist) mx = std::max(mx, (h_off[l + 1] - h_off[l]) + (noff[l + 1] - noff[l]));
+    }
+    const int64_t n_out = off[nlist];
+    DevBuf vecs2, ids2;
+    vecs2.ensure(std::max<size_t>(16, row_bytes() * n_out));
+    ids2.ensure(std::max<size_t>(16, sizeof(int64_t) * n_out));
+    out_off.ensure(sizeof(int64_t) * (nlist + 1));
+    ListMergeArgs m;
+    m.nlist = nlist;
+    m.lo = 0;
+    m.hi = nlist;
+    m.M = (int)row_bytes();
+    m.max_list = mx;
+    m.old_off = d_off.as<int64_t>();
+    m.old_codes = d_vecs.as<uint8_t>();
+    m.old_ids = d_ids.as<int64_t>();
+    m.new_off = new_off.as<int64_t>();
+    m.new_codes = vecs_n.as<uint8_t>();
+    m.new_ids = ids_n.as<int64_t>();
+    m.out_off = out_off.as<int64_t>();
+    m.out_codes = vecs2.as<uint8_t>();
+    m.out_ids = ids2.as<int64_t>();
+    HIPCHECK(image_merge_lists(m, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::swap(d_vecs.p, vecs2.p);
+    std::swap(d_vecs.bytes, vecs2.bytes);
+    std::swap(d_ids.p, ids2.p);
+    std::swap(d_ids.bytes, ids2.bytes);
+    std::swap(d_off.p, out_off.p);
+    std::swap(d_off.bytes, out_off.bytes);
+    img_n = n_out;
+    set_offsets(std::move(off));
+    q_lists.release();
+    q_ids.release();
+    q_n = q_cap = 0;
+    require(img_n == ntotal, "pending merge: image size disagrees with ntotal");
+  }
+
+  void check_search(int64_t n, const void* x, int k, const void* D, const void* I) const {
+    require(trained, "index is not trained");
+    require(n >= 0, "n must be >= 0");
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(n == 0 || (x && D && I), "null buffer");
+  }
+
+  // The search on device pointers, on stream s.  Iq non-null = preassigned probes
+  // [n][nprobe] (the handle's nprobe, as ivfpq_search_preassigned).
+  void search_dev(int64_t n, const float* x, int k, float* D, int64_t* I, const int64_t* Iq, hipStream_t s) {
+    flush_pending(s);
+    if (n == 0) return;
+    order_after(s);
+    if (img_n == 0) {
+      launch_ivfflat_fill_empty(D, I, n * k, ip(), s);
+      HIPCHECK(hipGetLastError());
+      mark_done(s);
+      return;
+    }
+    const int np = Iq ? nprobe : std::min(nprobe, nlist);
+    const IvfFlatPlan pl = ivfflat_plan(k, range_top[std::min(np, nlist)]);
+    // queries per chunk: the [c][nlist] coarse keys and buckets within kChunkBytes, the
+    // partial lists (12 bytes per entry, and the first merge round's output) within kPartialBytes
+    const size_t part_q = (size_t)pl.S * k * 12 * 2;
+    const int64_t qc = std::max<int64_t>(
+        1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)nlist * 8)), (int64_t)(kPartialBytes / part_q),
+                              (int64_t)(INT32_MAX / 2) / ((int64_t)pl.S * k)}));
+    if (!Iq) {
+      w_lists.ensure(sizeof(int64_t) * qc * np);
+      w_dis.ensure(sizeof(float) * qc * np);
+    }
+    p_cnt.ensure(sizeof(int32_t) * nlist);
+    p_bucket.ensure(sizeof(int2) * (size_t)nlist * qc);
+    p_items.ensure(sizeof(int32_t) * (nlist + 1));
+    p_used.ensure(sizeof(int32_t) * qc);
+    p_tau.ensure(sizeof(uint32_t) * qc);
+    p_partD.ensure(sizeof(float) * (size_t)pl.S * qc * k);
+    p_partI.ensure(sizeof(int64_t) * (size_t)pl.S * qc * k);
+    const size_t tmp_lists = (size_t)std::max(1, pl.S / pl.fan);
+    p_tmpD.ensure(sizeof(float) * tmp_lists * qc * k);
+    p_tmpI.ensure(sizeof(int64_t) * tmp_lists * qc * k);
+    for (int64_t q0 = 0; q0 < n; q0 += qc) {
+      const int64_t c = std::min(qc, n - q0);
+      const float* xq = x + q0 * d;
+      IvfFlatArgs a;
+      a.x = xq;
+      a.nq = c;
+      a.d = d;
+      a.vecs = d_vecs.as<float>();
+      a.ids = d_ids.as<int64_t>();
+      a.list_off = d_off.as<int64_t>();
+      a.nlist = nlist;
+      if (Iq) {
+        a.probes = Iq + q0 * np;
+      } else {
+        base.coarse_launch(xq, c, np, w_dis.as<float>(), w_lists.as<int64_t>(), s);
+        a.probes = w_lists.as<int64_t>();
+      }
+      a.nprobe = np;
+      a.dedup = Iq != nullptr;
+      a.k = k;
+      a.ip = ip();
+      a.cnt = p_cnt.as<int32_t>();
+      a.bucket = p_bucket.as<int2>();
+      a.item_off = p_items.as<int32_t>();
+      a.used = p_used.as<int32_t>();
+      a.tau = p_tau.as<uint32_t>();
+      a.partD = p_partD.as<float>();
+      a.partI = p_partI.as<int64_t>();
+      a.tmpD = p_tmpD.as<float>();
+      a.tmpI = p_tmpI.as<int64_t>();
+      a.D = D + q0 * k;
+      a.I = I + q0 * k;
+      launch_ivfflat_search(a, pl, s);
+      HIPCHECK(hipGetLastError());
+    }
+    mark_done(s);
+  }
+
+  // host-buffer search (copies in and out on the handle's stream)
+  void search_host(int64_t n, const float* x, int k, float* D, int64_t* I, const int64_t* Iq) {
+    if (n == 0) return;
+    quiesce();
+    w_x.ensure(sizeof(float) * n * d);
+    h_D.ensure(sizeof(float) * n * k);
+    h_I.ensure(sizeof(int64_t) * n * k);
+    HIPCHECK(hipMemcpyAsync(w_x.p, x, sizeof(float) * n * d, hipMemcpyHostToDevice, stream));
+    if (Iq) {
+      h_Iq.ensure(sizeof(int64_t) * n * nprobe);
+      HIPCHECK(hipMemcpyAsync(h_Iq.p, Iq, sizeof(int64_t) * n * nprobe, hipMemcpyHostToDevice, stream));
+    }
+    search_dev(n, w_x.as<float>(), k, h_D.as<float>(), h_I.as<int64_t>(), Iq ? h_Iq.as<int64_t>() : nullptr, stream);
+    HIPCHECK(hipMemcpyAsync(D, h_D.p, sizeof(float) * n * k, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipMemcpyAsync(I, h_I.p, sizeof(int64_t) * n * k, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+};
+
+namespace {
+void check_ivfflat(const ivfpq_ivfflat_index* h) { require(h != nullptr, "null index handle"); }
+}  // namespace
+
+extern "C" {
+
+int ivfpq_ivfflat_create(int d, int nlist, int metric, int device, ivfpq_ivfflat_index** out) {
+  return guarded([&] {
+    require(out != nullptr, "null output pointer");
+    require(d >= 4 && d <= 2048 && d % 4 == 0,
+            "IndexIVFFlat: d must be a multiple of 4 in [4, 2048] (d = " + std::to_string(d) + ")");
+    require(nlist >= 1, "nlist must be >= 1");
+    require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    require(device >= 0 && device < ndev, "device ordinal out of range");
+    DeviceGuard g(device);
+    auto h = std::make_unique<ivfpq_ivfflat_index>();
+    h->d = d;
+    h->nlist = nlist;
+    h->metric = metric;
+    h->device = device;
+    h->base.d = d;
+    h->base.nlist = nlist;
+    h->base.metric = metric;
+    h->base.device = device;
+    h->base.list_hi = nlist;
+    h->base.init_stream();
+    h->stream = h->base.stream;
+    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    h->clear_image();
+    *out = h.release();
+  });
+}
+
+int ivfpq_ivfflat_free(ivfpq_ivfflat_index* h) {
+  return guarded([&] {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->quiesce();
+    delete h;
+  });
+}
+
+int ivfpq_ivfflat_train(ivfpq_ivfflat_index* h, int64_t n, const float* x, int niter, uint64_t seed) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(x != nullptr && n > 0, "empty training set");
+    h->quiesce();
+    std::vector<float> cent((size_t)h->nlist * h->d);
+    h->base.kmeans(x, n, h->d, h->nlist, niter, seed, cent.data(), h->ip());  // ivfpq_train's coarse stage
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->centroids = std::move(cent);
+    h->upload_centroids();
+  });
+}
+
+int ivfpq_ivfflat_set_trained(ivfpq_ivfflat_index* h, const float* centroids) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(centroids != nullptr, "null centroids");
+    h->centroids.assign(centroids, centroids + (size_t)h->nlist * h->d);
+    h->upload_centroids();
+  });
+}
+
+int ivfpq_ivfflat_add(ivfpq_ivfflat_index* h, int64_t n, const float* x, const int64_t* ids) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(h->trained, "index is not trained");
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    h->add_dev(n, x, false, ids, false, h->stream);
+  });
+}
+
+int ivfpq_ivfflat_add_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, const int64_t* ids, void* stream) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(h->trained, "index is not trained");
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    h->add_dev(n, x, true, ids, true, stream ? (hipStream_t)stream : h->stream);
+  });
+}
+
+int ivfpq_ivfflat_reset(ivfpq_ivfflat_index* h) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->clear_image();
+  });
+}
+
+int ivfpq_ivfflat_set_nprobe(ivfpq_ivfflat_index* h, int nprobe) {
+  return guarded([&] {
+    check_ivfflat(h);
+    require(nprobe >= 1 && nprobe <= kMaxK, "nprobe must be in [1, " + std::to_string(kMaxK) + "]");
+    h->nprobe = nprobe;
+  });
+}
+
+int ivfpq_ivfflat_get_nprobe(const ivfpq_ivfflat_index* h) { return h ? h->nprobe : -1; }
+
+int ivfpq_ivfflat_search(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->check_search(n, x, k, D, I);
+    h->search_host(n, x, k, D, I, nullptr);
+  });
+}
+
+int ivfpq_ivfflat_search_preassigned(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
+                                     const float* Dq, float* D, int64_t* I) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    (void)Dq;  // the scan computes whole distances (IVFFlatScanner ignores the coarse distance)
+    h->check_search(n, x, k, D, I);
+    require(n == 0 || Iq, "null Iq");
+    for (int64_t i = 0; i < n * h->nprobe; i++) require(Iq[i] < h->nlist, "list id out of range in Iq");
+    h->search_host(n, x, k, D, I, Iq);
+  });
+}
+
+int ivfpq_ivfflat_search_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I,
+                                void* stream) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->check_search(n, x, k, D, I);
+    h->search_dev(n, x, k, D, I, nullptr, (hipStream_t)stream);
+  });
+}
+
+int ivfpq_ivfflat_search_preassigned_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k,
+                                            const int64_t* Iq, const float* Dq, float* D, int64_t* I, void* stream) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    (void)Dq;
+    h->check_search(n, x, k, D, I);
+    require(n == 0 || Iq, "null Iq");
+    h->search_dev(n, x, k, D, I, n ? Iq : nullptr, (hipStream_t)stream);
+  });
+}
+
+int64_t ivfpq_ivfflat_ntotal(const ivfpq_ivfflat_index* h) { return h ? h->ntotal : -1; }
+
+int ivfpq_ivfflat_is_trained(const ivfpq_ivfflat_index* h) { return h && h->trained ? 1 : 0; }
+
+int ivfpq_ivfflat_get_dims(const ivfpq_ivfflat_index* h, int* d, int* nlist, int* metric) {
+  return guarded([&] {
+    check_ivfflat(h);
+    if (d) *d = h->d;
+    if (nlist) *nlist = h->nlist;
+    if (metric) *metric = h->metric;
+  });
+}
+
+int ivfpq_ivfflat_get_centroids(const ivfpq_ivfflat_index* h, float* out) {
+  return guarded([&] {
+    check_ivfflat(h);
+    require(h->trained, "index is not trained");
+    require(out != nullptr, "null output pointer");
+    std::memcpy(out, h->centroids.data(), sizeof(float) * h->centroids.size());
+  });
+}
+
+int ivfpq_ivfflat_get_list_sizes(ivfpq_ivfflat_index* h, int64_t* out) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(out != nullptr, "null output pointer");
+    h->flush_pending(h->stream);
+    for (int l = 0; l < h->nlist; l++) out[l] = h->h_off[l + 1] - h->h_off[l];
+  });
+}
+
+int ivfpq_ivfflat_get_list(ivfpq_ivfflat_index* h, int list, float* vectors, int64_t* ids) {
+  return guarded([&] {
+    check_ivfflat(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    require(list >= 0 && list < h->nlist, "list id out of range");
+    h->flush_pending(h->stream);
+    h->quiesce();
+    const int64_t b = h->h_off[list], n = h->h_off[list + 1] - b;
+    if (n == 0) return;
+    if (vectors)
+      HIPCHECK(hipMemcpyAsync(vectors, h->d_vecs.as<float>() + b * h->d, h->row_bytes() * n, hipMemcpyDeviceToHost,
+                              h->stream));
+    if (ids)
+      HIPCHECK(hipMemcpyAsync(ids, h->d_ids.as<int64_t>() + b, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
   });
 }
 

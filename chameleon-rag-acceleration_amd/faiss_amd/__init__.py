@@ -12,6 +12,7 @@ from .index import (  # noqa: F401
     METRIC_L2,
     IndexFlatIP,
     IndexFlatL2,
+    IndexIVFFlat,
     IndexIVFPQ,
     IndexPQ,
     ParameterSpace,

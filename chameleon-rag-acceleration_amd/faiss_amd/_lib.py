@@ -113,6 +113,32 @@ SIGNATURES = {
     "ivfpq_pq_debug_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), c_i64p,
                                            ctypes.POINTER(ctypes.c_int), c_i64p]),
+    # IVF over raw vectors (IndexIVFFlat)
+    "ivfpq_ivfflat_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(c_handle)]),
+    "ivfpq_ivfflat_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfflat_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
+    "ivfpq_ivfflat_set_trained": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_ivfflat_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_i64p]),
+    "ivfpq_ivfflat_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "ivfpq_ivfflat_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfflat_set_nprobe": (ctypes.c_int, [c_handle, ctypes.c_int]),
+    "ivfpq_ivfflat_get_nprobe": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfflat_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_ivfflat_search_preassigned": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_i64p,
+                                                        c_f32p, c_f32p, c_i64p]),
+    "ivfpq_ivfflat_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_ivfflat_search_preassigned_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p,
+                                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_ivfflat_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_ivfflat_is_trained": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfflat_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 3),
+    "ivfpq_ivfflat_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_ivfflat_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
+    "ivfpq_ivfflat_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_f32p, c_i64p]),
 }
 
 

@@ -35,6 +35,12 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
       search_type i32 (0 = ST_PQ), encode_signs u8 (0), polysemous_ht i32 (0)
     "IxPT" may wrap it in place of the IndexIVFPQ.
 
+    "IwFl"                                   IndexIVFFlat (bench_gpu_1bn.py:575-578 ",Flat" keys)
+      the IVF header of "IwPQ": index header, nlist u64, nprobe u64, quantizer, direct map
+      "ilar" as above with code_size = 4 * d: a list's codes are its fp32 vectors
+      (no by_residual / code_size / PQ block)
+    Unpinned like the others: no Faiss-written "IwFl" file exists on the build machine.
+
 Parity is unpinned: no Faiss-written file exists in the reference or this image
 (the reference's ``*.index`` files are not shipped), so the tests check a
 hand-assembled byte layout and round trips, not a file from real Faiss.
@@ -47,6 +53,7 @@ import numpy as np
 
 FOURCC_IVFPQ = b"IwPQ"
 FOURCC_PQ = b"IxPq"
+FOURCC_IVFFLAT = b"IwFl"
 FOURCC_FLAT = {0: b"IxFI", 1: b"IxF2"}  # metric_type: 0 = INNER_PRODUCT, 1 = L2
 HEADER_DUMMY = 1 << 20
 
@@ -57,7 +64,7 @@ FOURCC_LINEAR = b"LTra"
 
 def is_faiss_file(path) -> bool:
     with open(path, "rb") as f:
-        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ)
+        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT)
 
 
 class _Reader:
@@ -109,7 +116,8 @@ def parse_index(buf: bytes) -> dict:
     """IndexIVFPQ or IndexPreTransform(LinearTransform..., IndexIVFPQ) bytes.
     IVF-PQ -> parse_ivfpq's dict with kind "ivfpq"; pre-transform -> {kind
     "pretransform", d, ntotal, metric, chain: [{A [d_out][d_in], b, have_bias,
-    d_in, d_out, is_trained}], index: the IVF-PQ dict}."""
+    d_in, d_out, is_trained}], index: the IVF-PQ dict}; IndexPQ -> kind "pq";
+    IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat)."""
     r = _Reader(buf)
     h = r.fourcc()
     if h == FOURCC_PRETRANSFORM:
@@ -130,6 +138,8 @@ def parse_index(buf: bytes) -> dict:
 
 
 def _parse_sub(r: "_Reader", h: bytes) -> dict:
+    if h == FOURCC_IVFFLAT:
+        return _parse_ivfflat(r)
     return _parse_pq(r) if h == FOURCC_PQ else _parse_ivfpq(r, h)
 
 
@@ -216,6 +226,25 @@ def _parse_ivfpq(r: _Reader, h: bytes) -> dict:
         raise RuntimeError("legacy IvPQ Faiss files (pre-1.5 inverted lists) are not supported")
     if h != FOURCC_IVFPQ:
         raise RuntimeError(f"not a Faiss IndexIVFPQ file (fourcc {h!r})")
+    d, ntotal, is_trained, metric, nlist, nprobe, xb = _parse_ivf_header(r)
+    by_residual = r.fmt("B") != 0
+    code_size = r.fmt("Q")
+    pd = r.fmt("Q")
+    M = r.fmt("Q")
+    nbits = r.fmt("Q")
+    cb = r.vector(np.float32)
+    if not by_residual:
+        raise RuntimeError("only by_residual IndexIVFPQ is supported")
+    if pd != d or nbits != 8 or code_size != M or (is_trained and cb.size != M * 256 * (d // M)):
+        raise RuntimeError("unsupported PQ shape (8-bit codes, code_size == M)")
+    lists = _parse_ilar(r, nlist, code_size, ntotal)
+    return {"kind": "ivfpq", "d": d, "nlist": nlist, "nprobe": nprobe, "M": M, "nbits": nbits, "metric": metric,
+            "is_trained": is_trained, "centroids": xb.reshape(nlist, d) if xb.size else xb,
+            "codebook": cb.reshape(M, 256, d // M) if cb.size else cb, "lists": lists}
+
+
+def _parse_ivf_header(r: _Reader):
+    """The part every IndexIVF writes first: index header, nlist, nprobe, flat quantizer, direct map."""
     d, ntotal, is_trained, metric = r.header()
     nlist = r.fmt("Q")
     nprobe = r.fmt("Q")
@@ -230,16 +259,11 @@ def _parse_ivfpq(r: _Reader, h: bytes) -> dict:
     dm = r.vector(np.int64)
     if dm_type != 0 or dm.size:
         raise RuntimeError("IVF direct maps are not supported")
-    by_residual = r.fmt("B") != 0
-    code_size = r.fmt("Q")
-    pd = r.fmt("Q")
-    M = r.fmt("Q")
-    nbits = r.fmt("Q")
-    cb = r.vector(np.float32)
-    if not by_residual:
-        raise RuntimeError("only by_residual IndexIVFPQ is supported")
-    if pd != d or nbits != 8 or code_size != M or (is_trained and cb.size != M * 256 * (d // M)):
-        raise RuntimeError("unsupported PQ shape (8-bit codes, code_size == M)")
+    return d, ntotal, is_trained, metric, nlist, nprobe, xb
+
+
+def _parse_ilar(r: _Reader, nlist, code_size, ntotal):
+    """ArrayInvertedLists -> [(ids i64[n], codes u8[n][code_size])] per list."""
     if r.fourcc() != b"ilar":
         raise RuntimeError("only ArrayInvertedLists ('ilar') are supported")
     il_n = r.fmt("Q")
@@ -269,9 +293,16 @@ def _parse_ivfpq(r: _Reader, h: bytes) -> dict:
         lists.append((ids, codes))
     if int(sizes.sum()) != ntotal:
         raise RuntimeError("inverted list sizes do not add up to ntotal")
-    return {"kind": "ivfpq", "d": d, "nlist": nlist, "nprobe": nprobe, "M": M, "nbits": nbits, "metric": metric,
-            "is_trained": is_trained, "centroids": xb.reshape(nlist, d) if xb.size else xb,
-            "codebook": cb.reshape(M, 256, d // M) if cb.size else cb, "lists": lists}
+    return lists
+
+
+def _parse_ivfflat(r: _Reader) -> dict:
+    """IndexIVFFlat after its fourcc -> {kind "ivfflat", d, nlist, nprobe, metric, is_trained,
+    centroids [nlist][d], lists: [(ids i64[n], vectors f32[n][d])]}."""
+    d, ntotal, is_trained, metric, nlist, nprobe, xb = _parse_ivf_header(r)
+    lists = [(ids, codes.view(np.float32).reshape(len(ids), d)) for ids, codes in _parse_ilar(r, nlist, 4 * d, ntotal)]
+    return {"kind": "ivfflat", "d": d, "nlist": nlist, "nprobe": nprobe, "metric": metric, "is_trained": is_trained,
+            "centroids": xb.reshape(nlist, d) if xb.size else xb, "lists": lists}
 
 
 def _header(d, ntotal, is_trained, metric):
@@ -287,14 +318,30 @@ def serialize_ivfpq(d, nlist, nprobe, M, nbits, metric, centroids, codebook, lis
     """The inverse of parse_ivfpq (sizes written as a "full" table, as Faiss does
     when more than half of the lists are non-empty, else "sprs")."""
     code_size = M * nbits // 8
+    out = _ivf_header(FOURCC_IVFPQ, d, nlist, nprobe, metric, centroids, lists, is_trained)
+    out += [struct.pack("<BQ", 1, code_size), struct.pack("<QQQ", d, M, nbits),
+            _vector(np.ascontiguousarray(codebook, np.float32).reshape(-1))]
+    return b"".join(out + _ilar(nlist, code_size, lists))
+
+
+def serialize_ivfflat(d, nlist, nprobe, metric, centroids, lists, is_trained=True) -> bytes:
+    """The inverse of parse_index for kind "ivfflat": lists = [(ids i64[n], vectors f32[n][d])].
+    Unpinned against Faiss, like the other layouts (see the module docstring)."""
+    out = _ivf_header(FOURCC_IVFFLAT, d, nlist, nprobe, metric, centroids, lists, is_trained)
+    flat = [(ids, np.ascontiguousarray(v, np.float32).reshape(len(ids), d).view(np.uint8)) for ids, v in lists]
+    return b"".join(out + _ilar(nlist, 4 * d, flat))
+
+
+def _ivf_header(fourcc, d, nlist, nprobe, metric, centroids, lists, is_trained):
     ntotal = sum(len(ids) for ids, _ in lists)
     cent = np.ascontiguousarray(centroids, np.float32).reshape(-1)
-    out = [FOURCC_IVFPQ, _header(d, ntotal, is_trained, metric), struct.pack("<QQ", nlist, nprobe),
-           FOURCC_FLAT[metric], _header(d, nlist if cent.size else 0, True, metric), _vector(cent),
-           struct.pack("<B", 0), _vector(np.zeros(0, np.int64)),
-           struct.pack("<BQ", 1, code_size), struct.pack("<QQQ", d, M, nbits),
-           _vector(np.ascontiguousarray(codebook, np.float32).reshape(-1)),
-           b"ilar", struct.pack("<QQ", nlist, code_size)]
+    return [fourcc, _header(d, ntotal, is_trained, metric), struct.pack("<QQ", nlist, nprobe),
+            FOURCC_FLAT[metric], _header(d, nlist if cent.size else 0, True, metric), _vector(cent),
+            struct.pack("<B", 0), _vector(np.zeros(0, np.int64))]
+
+
+def _ilar(nlist, code_size, lists):
+    out = [b"ilar", struct.pack("<QQ", nlist, code_size)]
     sizes = np.array([len(ids) for ids, _ in lists], np.uint64)
     nz = np.nonzero(sizes)[0]
     if len(nz) > nlist // 2:
@@ -305,7 +352,7 @@ def serialize_ivfpq(d, nlist, nprobe, M, nbits, metric, centroids, codebook, lis
         if len(ids):
             out.append(np.ascontiguousarray(codes, np.uint8).tobytes())
             out.append(np.ascontiguousarray(ids, np.int64).tobytes())
-    return b"".join(out)
+    return out
 
 
 def serialize_pretransform(d, metric, chain, sub: bytes, ntotal, is_trained=True) -> bytes:

@@ -14,6 +14,8 @@ The surface mirrors what Chameleon's callers use on ``faiss`` (SURVEY.md
   ``my_faiss_extract_scripts/extract_FPGA_required_data.py:174-248``);
 * ``IndexPQ(d, M, nbits, metric)`` (beir ``faiss_search.py:168-224``
   PQFaissSearch, plain or behind ``IndexPreTransform(OPQMatrix, ...)``);
+* ``IndexIVFFlat(quantizer, d, nlist, metric)`` (``bench_gpu_1bn.py:575-578``
+  index keys ending in ``,Flat``; ``compute_ground_truth.py:311`` "IVF1,Flat");
 * ``IndexFlatL2`` (the coarse quantizer; exact search on the GPU);
 * ``index_factory``, ``ParameterSpace``, ``read_index / write_index``,
   ``swig_ptr``, ``vector_to_array``, ``get_num_gpus``.
@@ -780,6 +782,213 @@ class IndexPQ:
                                                    ctypes.c_void_p(self._stream(x, stream))))
 
 
+class _FlatInvertedLists:
+    """index.invlists of an IndexIVFFlat (faiss ArrayInvertedLists read API): the
+    codes of a list are its vectors' bytes, ``code_size = 4 * d``."""
+
+    def __init__(self, owner):
+        self._o = owner
+
+    @property
+    def nlist(self):
+        return self._o.nlist
+
+    @property
+    def code_size(self):
+        return 4 * self._o.d
+
+    def list_sizes(self):
+        out = np.empty(self._o.nlist, np.int64)
+        _lib.check(_lib.load().ivfpq_ivfflat_get_list_sizes(self._o._h, _ptr(out, _lib.c_i64p)))
+        return out
+
+    def list_size(self, l):
+        return int(self.list_sizes()[l])
+
+    def _get(self, l):
+        n = self.list_size(l)
+        vecs = np.empty((n, self._o.d), np.float32)
+        ids = np.empty(n, np.int64)
+        _lib.check(_lib.load().ivfpq_ivfflat_get_list(self._o._h, int(l), _ptr(vecs, _lib.c_f32p),
+                                                      _ptr(ids, _lib.c_i64p)))
+        return vecs, ids
+
+    def get_vectors(self, l):
+        """The list's vectors float32 [size][d], label-sorted."""
+        return self._get(l)[0]
+
+    def get_codes(self, l):
+        return self._get(l)[0].view(np.uint8).reshape(-1)
+
+    def get_ids(self, l):
+        return self._get(l)[1]
+
+    imbalance_factor = _InvertedLists.imbalance_factor
+
+
+class IndexIVFFlat:
+    """faiss.IndexIVFFlat: IVF over the raw fp32 vectors with exact distances
+    (``bench_gpu_1bn.py:575-578`` index keys ending in ``,Flat``; the ``IVF1,Flat``
+    ground truth of ``compute_ground_truth.py:311``).  The coarse quantizer is the
+    IndexIVFPQ one; the lists live in HBM only."""
+
+    def __init__(self, quantizer, d, nlist, metric=METRIC_L2, device=None):
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.metric_type = metric
+        self.device = _default_device() if device is None else int(device)
+        if quantizer is None:
+            quantizer = (IndexFlatIP if metric == METRIC_INNER_PRODUCT else IndexFlatL2)(d, self.device)
+        self.quantizer = quantizer
+        self.parallel_mode = 0
+        self.verbose = False
+        self.niter_coarse = 25
+        self.seed = 1234
+        h = _lib.c_handle()
+        _lib.check(_lib.load().ivfpq_ivfflat_create(self.d, self.nlist, metric, self.device, ctypes.byref(h)))
+        self._h = h
+        self.invlists = _FlatInvertedLists(self)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ivfpq_ivfflat_free(h)
+            self._h = None
+
+    @property
+    def ntotal(self):
+        return int(_lib.load().ivfpq_ivfflat_ntotal(self._h))
+
+    @property
+    def is_trained(self):
+        return bool(_lib.load().ivfpq_ivfflat_is_trained(self._h))
+
+    @property
+    def nprobe(self):
+        return int(_lib.load().ivfpq_ivfflat_get_nprobe(self._h))
+
+    @nprobe.setter
+    def nprobe(self, p):
+        _lib.check(_lib.load().ivfpq_ivfflat_set_nprobe(self._h, int(p)))
+
+    @property
+    def code_size(self):
+        return 4 * self.d
+
+    def centroids(self):
+        c = np.empty((self.nlist, self.d), np.float32)
+        _lib.check(_lib.load().ivfpq_ivfflat_get_centroids(self._h, _ptr(c, _lib.c_f32p)))
+        return c
+
+    _sync_quantizer = IndexIVFPQ._sync_quantizer
+
+    # ----------------------------------------------------------- build path
+    def train(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_ivfflat_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_coarse,
+                                                   self.seed))
+        self._sync_quantizer()
+
+    def set_trained(self, centroids):
+        """Install trained coarse centroids [nlist][d]."""
+        c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
+        _lib.check(_lib.load().ivfpq_ivfflat_set_trained(self._h, _ptr(c, _lib.c_f32p)))
+        self._sync_quantizer()
+
+    def add(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_ivfflat_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), None))
+
+    def add_with_ids(self, x, ids):
+        x = _f32(x, self.d)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        if ids.shape[0] != x.shape[0]:
+            raise RuntimeError("ids and x have different lengths")
+        _lib.check(_lib.load().ivfpq_ivfflat_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(ids, _lib.c_i64p)))
+
+    def reset(self):
+        _lib.check(_lib.load().ivfpq_ivfflat_reset(self._h))
+
+    # ------------------------------------------------------------ search path
+    _check_k = IndexIVFPQ._check_k
+    _check_dev = IndexIVFPQ._check_dev
+    _dev_outputs = IndexIVFPQ._dev_outputs
+    _stream = IndexIVFPQ._stream
+    search_preassigned = IndexIVFPQ.search_preassigned
+
+    def search(self, x, k):
+        x = _f32(x, self.d)
+        self._check_k(k)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _lib.check(_lib.load().ivfpq_ivfflat_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
+                                                    _ptr(I, _lib.c_i64p)))
+        return D, I
+
+    def _search_preassigned(self, x, k, Iq, Dq=None):
+        """Dq is accepted and ignored: the scan computes whole distances."""
+        x = _f32(np.asarray(x).reshape(-1, self.d), self.d)
+        self._check_k(k)
+        n = x.shape[0]
+        Iq = np.ascontiguousarray(Iq, np.int64).reshape(n, -1)
+        if Iq.shape[1] != self.nprobe:
+            raise RuntimeError(f"Iq must have nprobe={self.nprobe} columns, got {Iq.shape[1]}")
+        Dqp = None
+        if Dq is not None:
+            Dq = np.ascontiguousarray(Dq, np.float32).reshape(Iq.shape)
+            Dqp = _ptr(Dq, _lib.c_f32p)
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _lib.check(_lib.load().ivfpq_ivfflat_search_preassigned(self._h, n, _ptr(x, _lib.c_f32p), int(k),
+                                                                _ptr(Iq, _lib.c_i64p), Dqp, _ptr(D, _lib.c_f32p),
+                                                                _ptr(I, _lib.c_i64p)))
+        return D, I
+
+    # ------------------------------------------------- device (torch) entry points
+    def search_device(self, x, k, D=None, I=None, stream=None):
+        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
+        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
+        import torch
+
+        self._check_k(k)
+        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
+        D, I = self._dev_outputs(x, k, D, I)
+        _lib.check(_lib.load().ivfpq_ivfflat_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
+                                                           I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+    def search_preassigned_device(self, x, k, Iq, Dq=None, D=None, I=None, stream=None):
+        """search_preassigned with HBM-resident inputs (Dq is checked and ignored)."""
+        import torch
+
+        self._check_k(k)
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.float32, (n, self.d))
+        self._check_dev(Iq, "Iq", torch.int64, (n, self.nprobe))
+        if Dq is not None:
+            self._check_dev(Dq, "Dq", torch.float32, (n, self.nprobe))
+        D, I = self._dev_outputs(x, k, D, I)
+        _lib.check(_lib.load().ivfpq_ivfflat_search_preassigned_device(
+            self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
+            D.data_ptr(), I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+    def add_device(self, x, ids=None, stream=None):
+        """add / add_with_ids with the vectors already in HBM (torch float32 CUDA
+        tensor [n, d]; ids: int64 CUDA tensor [n] or None for sequential ids);
+        returns once the vectors are in place."""
+        import torch
+
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.float32, (n, self.d))
+        if ids is not None:
+            self._check_dev(ids, "ids", torch.int64, (n,))
+        _lib.check(_lib.load().ivfpq_ivfflat_add_device(self._h, n, x.data_ptr(),
+                                                        ids.data_ptr() if ids is not None else None,
+                                                        ctypes.c_void_p(self._stream(x, stream))))
+
+
 def decode_pq(codebook, codes):
     """ProductQuantizer::decode: codebook [M][256][dsub], codes uint8 [n][M] -> float32 [n][M * dsub]."""
     M, _, dsub = codebook.shape
@@ -813,6 +1022,7 @@ def merge_topk_device(Ds, Is, metric=METRIC_L2, stream=None):
 
 _PQ_FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?PQ(\d+)(?:x(\d+))?$")
 _FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x(\d+))?$")
+_IVFFLAT_FACTORY_RE = re.compile(r"^IVF(\d+),Flat$")
 
 
 def parse_factory(key):
@@ -841,12 +1051,23 @@ def parse_pq_factory(key):
     return base + (int(m.group(1)), int(m.group(2)) if m.group(2) else -1)
 
 
+def parse_ivfflat_factory(key):
+    """'IVF<nlist>,Flat' -> nlist; None for any other key."""
+    m = _IVFFLAT_FACTORY_RE.match(key.replace(" ", ""))
+    return int(m.group(1)) if m else None
+
+
 def index_factory(d, key, metric=METRIC_L2, device=None):
     """faiss.index_factory(d, "IVF1024,PQ16") (bench_polysemous_1bn.py:272), the
-    OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), and the flat
-    "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224)."""
+    OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), the flat
+    "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
+    "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
+    truth of compute_ground_truth.py:311)."""
     from .transform import IndexPreTransform, OPQMatrix
 
+    nlist = parse_ivfflat_factory(key)
+    if nlist is not None:
+        return IndexIVFFlat(None, d, nlist, metric, device)
     f = parse_pq_factory(key)
     if f is not None:
         if len(f) == 2:
@@ -895,13 +1116,21 @@ def _pq_bytes(index):
                                  index._codes(0, index.ntotal))
 
 
+def _ivfflat_bytes(index):
+    if not index.is_trained:
+        raise RuntimeError("IndexIVFFlat is written once trained")
+    inv = index.invlists
+    lists = [(inv.get_ids(l), inv.get_vectors(l)) for l in range(index.nlist)]
+    return faiss_io.serialize_ivfflat(index.d, index.nlist, index.nprobe, index.metric_type, index.centroids(), lists)
+
+
 def _sub_bytes(index):
     return _pq_bytes(index) if isinstance(index, IndexPQ) else _ivfpq_bytes(index)
 
 
 def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
-    IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
+    IndexIVFFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform
 
@@ -915,6 +1144,10 @@ def write_index(index, path, fmt="faiss"):
         if fmt != "faiss":
             raise RuntimeError("IndexPQ is written in the Faiss layout")
         buf = _pq_bytes(index)
+    elif isinstance(index, IndexIVFFlat):
+        if fmt != "faiss":
+            raise RuntimeError("IndexIVFFlat is written in the Faiss layout")
+        buf = _ivfflat_bytes(index)
     elif fmt == "native" or not index.is_trained:
         _lib.check(_lib.load().ivfpq_save(index._h, str(path).encode()))
         return
@@ -948,12 +1181,27 @@ def _pq_from_dict(z, device):
     return idx
 
 
+def _ivfflat_from_dict(z, device):
+    """The lists' vectors are added with their ids: each is assigned again by the
+    coarse quantizer, which puts a vector this library wrote back into its list."""
+    idx = IndexIVFFlat(None, z["d"], z["nlist"], z["metric"], device)
+    if z["is_trained"]:
+        idx.set_trained(z["centroids"])
+        nonempty = [(ids, vecs) for ids, vecs in z["lists"] if len(ids)]
+        if nonempty:
+            idx.add_with_ids(np.concatenate([v for _, v in nonempty]), np.concatenate([i for i, _ in nonempty]))
+    idx.nprobe = max(1, min(int(z["nprobe"]), z["nlist"]))
+    return idx
+
+
 def _index_from_dict(z, device):
+    if z["kind"] == "ivfflat":
+        return _ivfflat_from_dict(z, device)
     return _pq_from_dict(z, device) if z["kind"] == "pq" else _ivfpq_from_dict(z, device)
 
 
 def read_index(path, device=None):
-    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexPreTransform ("IxPT")
+    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexPreTransform ("IxPT")
     file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
     if faiss_io.is_faiss_file(path):

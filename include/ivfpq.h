@@ -269,6 +269,64 @@ int ivfpq_pq_get_codebook(const ivfpq_pq_index* h, float* out); /* [M][256][d/M]
 /* codes [i0, i0 + n) of the image, uint8 [n][M] (IndexPQ.codes) */
 int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out);
 
+/* ---- IVF over raw vectors: faiss.IndexIVFFlat(quantizer, d, nlist, metric) ---------
+ * (bench_gpu_1bn.py:575-578 and its siblings bench_gpu_1bn_SC.py:580,
+ * bench_gpu_performance_OSDI.py:556, gpu_infinite_loop.py:590: an index key ending in
+ * ",Flat"; bench_on_disk_performance.py:37; the exact ground truth of
+ * compute_ground_truth.py:311 and generate_SYN_dataset.py:157, 285: "IVF1,Flat").
+ * The coarse quantizer, its training and the probe selection are the IVF-PQ handle's;
+ * the inverted lists hold the fp32 vectors themselves (code size 4 d bytes), and a
+ * search computes fvec_L2sqr / fvec_inner_product of the query with every vector of
+ * every probed list in Faiss's AVX order (IVFFlatScanner).  d must be a multiple of 4
+ * in [4, 2048]; nlist >= 1; nprobe is clamped to nlist; k <= 1024; the index holds
+ * fewer than 2^31 - 1 vectors; fp32 storage only.  Same conventions, errors and
+ * locking as above (one mutex per handle); device calls of one handle on different
+ * streams run one after the other.  The vectors live in HBM only. */
+typedef struct ivfpq_ivfflat_index ivfpq_ivfflat_index;
+
+int ivfpq_ivfflat_create(int d, int nlist, int metric, int device, ivfpq_ivfflat_index** out);
+int ivfpq_ivfflat_free(ivfpq_ivfflat_index* h);
+/* Index.train(x) (bench_gpu_1bn.py:592): the coarse k-means of ivfpq_train alone,
+ * same seed rule -- the centroids equal an IVF-PQ index's for the same x, niter, seed. */
+int ivfpq_ivfflat_train(ivfpq_ivfflat_index* h, int64_t n, const float* x, int niter, uint64_t seed);
+/* Install trained centroids [nlist][d] (quantizer.xb, e.g. from a Faiss .index). */
+int ivfpq_ivfflat_set_trained(ivfpq_ivfflat_index* h, const float* centroids);
+/* Index.add(x) / add_with_ids(x, ids) (bench_gpu_1bn.py:598-658, the base set added in
+ * slices).  ids == NULL assigns ntotal, ntotal+1, ...  The list is the coarse top-1 of
+ * the search's coarse kernels, the stored code the vector's own bytes. */
+int ivfpq_ivfflat_add(ivfpq_ivfflat_index* h, int64_t n, const float* x, const int64_t* ids);
+/* The same with x (and ids, nullable) in HBM, on `stream` (hipStream_t, NULL = the
+ * handle's stream); returns when the vectors are in place. */
+int ivfpq_ivfflat_add_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, const int64_t* ids, void* stream);
+/* Index.reset(): drop the vectors, keep the centroids. */
+int ivfpq_ivfflat_reset(ivfpq_ivfflat_index* h);
+/* index.nprobe = p / ParameterSpace nprobe (bench_gpu_1bn.py:783-784); 1..1024, clamped to nlist at search. */
+int ivfpq_ivfflat_set_nprobe(ivfpq_ivfflat_index* h, int nprobe);
+int ivfpq_ivfflat_get_nprobe(const ivfpq_ivfflat_index* h);
+/* Index.search(x, k) -> (D, I) (bench_gpu_1bn.py:788-806; compute_ground_truth.py:311).
+ * Host buffers.  Queries are taken in chunks so that the workspace stays bounded. */
+int ivfpq_ivfflat_search(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* IndexIVF::search_preassigned / faiss.contrib.ivf_tools.search_preassigned
+ * (faiss_retriever.py:217-223, 265).  Iq: int64 [n][nprobe] list ids (-1 = skip; a list
+ * id repeated in a row is scanned once); Dq is accepted and ignored (IVFFlatScanner
+ * does not use the coarse distance). */
+int ivfpq_ivfflat_search_preassigned(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
+                                     const float* Dq, float* D, int64_t* I);
+/* Device-pointer variants, launched on `stream` (hipStream_t, NULL = the default stream). */
+int ivfpq_ivfflat_search_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I,
+                                void* stream);
+int ivfpq_ivfflat_search_preassigned_device(ivfpq_ivfflat_index* h, int64_t n, const float* x, int k,
+                                            const int64_t* Iq, const float* Dq, float* D, int64_t* I, void* stream);
+/* Accessors (index.ntotal, is_trained, d / nlist / metric_type, quantizer.xb). */
+int64_t ivfpq_ivfflat_ntotal(const ivfpq_ivfflat_index* h);
+int ivfpq_ivfflat_is_trained(const ivfpq_ivfflat_index* h);
+int ivfpq_ivfflat_get_dims(const ivfpq_ivfflat_index* h, int* d, int* nlist, int* metric);
+int ivfpq_ivfflat_get_centroids(const ivfpq_ivfflat_index* h, float* out); /* [nlist][d] */
+int ivfpq_ivfflat_get_list_sizes(ivfpq_ivfflat_index* h, int64_t* out);    /* [nlist] (invlists.list_size) */
+/* invlists.get_codes / get_ids of one list, label-sorted: vectors float32 [size][d],
+ * ids int64 [size] (either nullable), copied from the device image. */
+int ivfpq_ivfflat_get_list(ivfpq_ivfflat_index* h, int list, float* vectors, int64_t* ids);
+
 #ifdef __cplusplus
 }
 #endif

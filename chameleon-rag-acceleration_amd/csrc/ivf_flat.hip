@@ -13,7 +13,7 @@
 //    scalar cache.  Every lane carries Faiss's eight interleaved accumulators per
 //    query from one 32-dimension step to the next, so the sum is tree<>'s whatever d;
 //  * each wave keeps the k best (key, image position) of its rows in registers (the
-//    bitonic wave top-k of ivfpq_kernels.hip, restated here for int32 positions;
+//    bitonic wave top-k of ivfpq_kernels.hip, restated in scan_topk.h for int32 positions;
 //    inside one row range position order is label order) and writes them sorted with
 //    their int64 labels; launch_merge_topk, composed in rounds, merges the partial
 //    lists by (key, label).  No distance is written to memory.
@@ -31,172 +31,11 @@
 
 #include "ivf_flat.h"
 #include "ivfpq_kernels.h"
+#include "scan_topk.h"  // the wave top-k, the shared bound, the candidate queue, the merge rounds
 
 namespace chivf {
 
 namespace {
-
-constexpr float kInf = __builtin_huge_valf();
-constexpr int kNone = INT32_MAX;  // "no candidate" position (real positions are < 2^31 - 1)
-
-enum { K_IP = 0, K_L2 = 1 };
-
-// ---- wave top-k in registers (int32 positions) ---------------------------------
-__device__ __forceinline__ bool lexless(float ad, int ai, float bd, int bi) {
-  return (ad < bd) | ((ad == bd) & (ai < bi));
-}
-__device__ __forceinline__ float readlane_f(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-template <int CTRL>
-__device__ __forceinline__ int dmov(int v) {
-  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false);
-}
-// lane ^ J exchange on the VALU: DPP for J <= 8, the gfx950 row / half swaps above
-template <int J>
-__device__ __forceinline__ int xor_i(int v) {
-  if constexpr (J == 1) return dmov<0xB1>(v);
-  else if constexpr (J == 2) return dmov<0x4E>(v);
-  else if constexpr (J == 4) return dmov<0x1B>(dmov<0x141>(v));
-  else if constexpr (J == 8) return dmov<0x128>(v);
-  else if constexpr (J == 16) {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((__lane_id() & 16) ? r[0] : r[1]);
-  } else {
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((__lane_id() & 32) ? r[0] : r[1]);
-  }
-}
-template <int J>
-__device__ __forceinline__ float xor_f(float v) { return __int_as_float(xor_i<J>(__float_as_int(v))); }
-__device__ __forceinline__ int rev64_i(int v) { return xor_i<16>(xor_i<32>(dmov<0x140>(v))); }
-__device__ __forceinline__ float rev64_f(float v) { return __int_as_float(rev64_i(__float_as_int(v))); }
-
-// A wave's running k best (key, position) pairs, sorted ascending across R rows x 64
-// lanes (logical index r * 64 + lane); k <= 64 * R.
-template <int R>
-struct WaveTopK {
-  float d[R];
-  int id[R];
-  float td;  // the admission threshold: the current k-th best, or the query's shared bound where that is lower
-  int ti;
-  int krow, klane;
-  float cap;  // the query's shared bound as last read (every key above it is outside the final top-k)
-  float pub;  // the k-th best this wave last published to the shared bound
-
-  __device__ __forceinline__ void init(int k) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      d[r] = kInf;
-      id[r] = kNone;
-    }
-    td = kInf;
-    ti = kNone;
-    cap = kInf;
-    pub = kInf;
-    krow = (k - 1) >> 6;
-    klane = (k - 1) & 63;
-  }
-  // a key equal to the bound may still be among the k best (ties go by label): (c, none) admits it
-  __device__ __forceinline__ void set_cap(float c) {
-    cap = fminf(cap, c);
-    if (td > cap) {
-      td = cap;
-      ti = kNone;
-    }
-  }
-  __device__ __forceinline__ void refresh_tau() {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      if (r == krow) {
-        td = readlane_f(d[r], klane);
-        ti = __builtin_amdgcn_readlane(id[r], klane);
-      }
-    }
-    if (td > cap) {
-      td = cap;
-      ti = kNone;
-    }
-  }
-  // once the wave holds k rows, its k-th key bounds the query's final k-th key: lower the shared bound to it
-  __device__ __forceinline__ void publish(uint32_t* tau_q, int lane);
-};
-
-template <int KK, int J>
-__device__ __forceinline__ void bitonic_step(float& cd, int& ci, int lane) {
-  const float od = xor_f<J>(cd);
-  const int oi = xor_i<J>(ci);
-  const bool want_min = ((lane & J) == 0) == ((lane & KK) == 0);
-  const bool o_lt = lexless(od, oi, cd, ci);
-  const bool c_lt = lexless(cd, ci, od, oi);
-  const bool take = (want_min & o_lt) | (!want_min & c_lt);
-  cd = take ? od : cd;
-  ci = take ? oi : ci;
-}
-template <int KK, int J>
-__device__ __forceinline__ void bitonic_steps(float& cd, int& ci, int lane) {
-  if constexpr (J >= 1) {
-    bitonic_step<KK, J>(cd, ci, lane);
-    bitonic_steps<KK, J / 2>(cd, ci, lane);
-  }
-}
-template <int KK>
-__device__ __forceinline__ void bitonic_sort64(float& cd, int& ci, int lane) {
-  if constexpr (KK <= 64) {
-    bitonic_steps<KK, KK / 2>(cd, ci, lane);
-    bitonic_sort64<KK * 2>(cd, ci, lane);
-  }
-}
-
-// Merge up to 64 candidates (one per lane; (inf, none) = no candidate) into the R-row
-// top-k: bitonic sort of the candidates, then per row the reverse-min + bitonic merge,
-// the upper half carried to the next row.
-template <int R>
-__device__ __forceinline__ void bulk_merge_rows(WaveTopK<R>& tk, float cd, int ci, int lane) {
-  bitonic_sort64<2>(cd, ci, lane);
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const float rd = rev64_f(cd);
-    const int ri = rev64_i(ci);
-    const bool t = lexless(rd, ri, tk.d[r], tk.id[r]);
-    const float lo_d = t ? rd : tk.d[r], hi_d = t ? tk.d[r] : rd;
-    const int lo_i = t ? ri : tk.id[r], hi_i = t ? tk.id[r] : ri;
-    tk.d[r] = lo_d;
-    tk.id[r] = lo_i;
-    bitonic_steps<128, 32>(tk.d[r], tk.id[r], lane);  // KK = 128: every lane ascending
-    if (r + 1 < R) {
-      cd = hi_d;
-      ci = hi_i;
-      bitonic_steps<128, 32>(cd, ci, lane);
-    }
-  }
-  tk.refresh_tau();
-}
-
-// The shared bound of a query: the lowest k-th key any wave has reached so far in this
-// batch, as order-preserving bits lowered by atomicMin (all-ones = none yet).  It only
-// prunes: a row above it cannot be among the k best, whichever waves have published, so
-// the merged result does not depend on the timing.  Read once per wave (readfirstlane).
-__device__ __forceinline__ uint32_t key_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tau_get(const uint32_t* tau_q) {
-  const uint32_t u = __builtin_amdgcn_readfirstlane(
-      __hip_atomic_load(tau_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  return u == 0xFFFFFFFFu ? kInf : __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-template <int R>
-__device__ __forceinline__ void WaveTopK<R>::publish(uint32_t* tau_q, int lane) {
-  float kth = kInf;
-#pragma unroll
-  for (int r = 0; r < R; r++)
-    if (r == krow) kth = readlane_f(d[r], klane);
-  if (kth < pub) {  // uniform
-    pub = kth;
-    if (lane == 0) __hip_atomic_fetch_min(tau_q, key_bits(kth), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
 
 // -------------------------------------------------------------------- planning
 __device__ __forceinline__ int range_count(int64_t rows) {
@@ -284,30 +123,6 @@ constexpr int kDc = 32;             // dimensions per staged step (a multiple of
 constexpr int kRowStride = kDc + 4; // floats per LDS row: 16-byte aligned, and consecutive rows start 4 banks apart
 constexpr int kTile = 256;          // rows per pass: one per thread
 constexpr int kLoads = kTile * kDc / 4 / 256;  // 16-byte loads per thread and step
-constexpr int kQueue = 64 + 64;     // queued candidates per (wave, query): < 64 pending + a pass's pushes
-
-// The first min(n, 64) candidates of a wave's queue (q_d, q_i) into its top-k, the
-// rest moved to the front; n becomes the number left.
-template <int R>
-__device__ __forceinline__ void drain_queue(WaveTopK<R>& tk, int& n, float* q_d, int* q_i, int lane) {
-  __builtin_amdgcn_wave_barrier();
-  const bool have = lane < n;
-  const float cd = have ? q_d[lane] : kInf;
-  const int ci = have ? q_i[lane] : kNone;
-  const int rem = max(n - 64, 0);
-  const bool mv = lane < rem;
-  const float md = mv ? q_d[64 + lane] : kInf;
-  const int mi = mv ? q_i[64 + lane] : kNone;
-  __builtin_amdgcn_wave_barrier();
-  if (mv) {
-    q_d[lane] = md;
-    q_i[lane] = mi;
-  }
-  __builtin_amdgcn_wave_barrier();
-  n = rem;
-  const bool pass = lexless(cd, ci, tk.td, tk.ti);  // the bound may have moved since the push
-  if (__ballot(pass)) bulk_merge_rows<R>(tk, pass ? cd : kInf, pass ? ci : kNone, lane);
-}
 
 // Persistent over work items: workgroup b takes items b, b + gridDim.x, ...
 // LDS: the 36 KiB tile, plus G KiB of candidate queues per wave when R > 1.
@@ -575,28 +390,7 @@ void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& p, hipStream
     launch_scan_kind<K_IP>(a, p, s);
   else
     launch_scan_kind<K_L2>(a, p, s);
-  // Merge rounds.  A round over S lists [S][nq][k] with fan f merges, for every j below
-  // S / f, the lists j, j + S / f, j + 2 S / f, ... -- read as [f][nq * S / f][k] they are
-  // one launch_merge_topk call whose output is the next round's [S / f][nq][k].
-  const float* inD = a.partD;
-  const int64_t* inI = a.partI;
-  int S = p.S;
-  bool to_tmp = true;
-  while (true) {
-    const int f = std::min(S, p.fan);
-    const int left = S / f;
-    if (left == 1) {
-      launch_merge_topk(f, a.nq, a.k, inD, inI, a.D, a.I, s, a.ip);
-      break;
-    }
-    float* outD = to_tmp ? a.tmpD : a.partD;
-    int64_t* outI = to_tmp ? a.tmpI : a.partI;
-    launch_merge_topk(f, a.nq * left, a.k, inD, inI, outD, outI, s, a.ip);
-    inD = outD;
-    inI = outI;
-    S = left;
-    to_tmp = !to_tmp;
-  }
+  merge_partial_lists(a.partD, a.partI, a.tmpD, a.tmpI, p.S, p.fan, a.nq, a.k, a.ip, a.D, a.I, s);
 }
 
 }  // namespace chivf

@@ -15,7 +15,9 @@ from .index import (  # noqa: F401
     IndexIVFFlat,
     IndexIVFPQ,
     IndexPQ,
+    IndexScalarQuantizer,
     ParameterSpace,
+    ScalarQuantizer,
     downcast_index,
     extract_index_ivf,
     get_num_gpus,

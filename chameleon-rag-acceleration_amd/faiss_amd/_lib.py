@@ -139,6 +139,26 @@ SIGNATURES = {
     "ivfpq_ivfflat_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
     "ivfpq_ivfflat_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
     "ivfpq_ivfflat_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_f32p, c_i64p]),
+    # flat scalar quantizer (IndexScalarQuantizer)
+    "ivfpq_sq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(c_handle)]),
+    "ivfpq_sq_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_sq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
+    "ivfpq_sq_set_trained": (ctypes.c_int, [c_handle, c_f32p, ctypes.c_int64]),
+    "ivfpq_sq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
+    "ivfpq_sq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_sq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
+    "ivfpq_sq_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_sq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_sq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_sq_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_sq_is_trained": (ctypes.c_int, [c_handle]),
+    "ivfpq_sq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 4),
+    "ivfpq_sq_get_trained": (ctypes.c_int, [c_handle, c_f32p, c_i64p]),
+    "ivfpq_sq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
+    "ivfpq_sq_encode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_u8p]),
+    "ivfpq_sq_decode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, c_f32p]),
 }
 
 

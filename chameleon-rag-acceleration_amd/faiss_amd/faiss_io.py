@@ -41,6 +41,14 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
       (no by_residual / code_size / PQ block)
     Unpinned like the others: no Faiss-written "IwFl" file exists on the build machine.
 
+    "IxSQ"                                   IndexScalarQuantizer (beir faiss_search.py:415-459)
+      index header
+      SQ:          qtype i32, rangestat i32 (0 = RS_minmax), rangestat_arg f32 (0), d u64, code_size u64,
+                   trained = u64 count + f32[count]   ([vmin (d), vdiff (d)] | [vmin, vdiff] | empty)
+      codes = u64 count + u8[ntotal * code_size]
+    "IxPT" may wrap it too.
+    Unpinned like the others: no Faiss-written "IxSQ" file exists on the build machine.
+
 Parity is unpinned: no Faiss-written file exists in the reference or this image
 (the reference's ``*.index`` files are not shipped), so the tests check a
 hand-assembled byte layout and round trips, not a file from real Faiss.
@@ -54,6 +62,8 @@ import numpy as np
 FOURCC_IVFPQ = b"IwPQ"
 FOURCC_PQ = b"IxPq"
 FOURCC_IVFFLAT = b"IwFl"
+FOURCC_SQ = b"IxSQ"
+SQ_QT_8BIT, SQ_QT_8BIT_UNIFORM, SQ_QT_FP16 = 0, 2, 4  # the scalar quantizer types that are read and written
 FOURCC_FLAT = {0: b"IxFI", 1: b"IxF2"}  # metric_type: 0 = INNER_PRODUCT, 1 = L2
 HEADER_DUMMY = 1 << 20
 
@@ -64,7 +74,7 @@ FOURCC_LINEAR = b"LTra"
 
 def is_faiss_file(path) -> bool:
     with open(path, "rb") as f:
-        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT)
+        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT, FOURCC_SQ)
 
 
 class _Reader:
@@ -117,7 +127,7 @@ def parse_index(buf: bytes) -> dict:
     IVF-PQ -> parse_ivfpq's dict with kind "ivfpq"; pre-transform -> {kind
     "pretransform", d, ntotal, metric, chain: [{A [d_out][d_in], b, have_bias,
     d_in, d_out, is_trained}], index: the IVF-PQ dict}; IndexPQ -> kind "pq";
-    IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat)."""
+    IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat); IndexScalarQuantizer -> kind "sq" (_parse_sq)."""
     r = _Reader(buf)
     h = r.fourcc()
     if h == FOURCC_PRETRANSFORM:
@@ -140,6 +150,8 @@ def parse_index(buf: bytes) -> dict:
 def _parse_sub(r: "_Reader", h: bytes) -> dict:
     if h == FOURCC_IVFFLAT:
         return _parse_ivfflat(r)
+    if h == FOURCC_SQ:
+        return _parse_sq(r)
     return _parse_pq(r) if h == FOURCC_PQ else _parse_ivfpq(r, h)
 
 
@@ -185,6 +197,49 @@ def serialize_pq(d, M, nbits, metric, codebook, codes, is_trained=True) -> bytes
                      struct.pack("<QQQ", d, M, nbits),
                      _vector(np.ascontiguousarray(codebook, np.float32).reshape(-1)), _vector(codes),
                      struct.pack("<iBi", 0, 0, 0)])
+
+
+def sq_shape(qtype, d):
+    """(code_size, len(trained)) of a supported scalar quantizer type."""
+    if qtype == SQ_QT_FP16:
+        return 2 * d, 0
+    if qtype == SQ_QT_8BIT:
+        return d, 2 * d
+    if qtype == SQ_QT_8BIT_UNIFORM:
+        return d, 2
+    raise RuntimeError(f"unsupported scalar quantizer type {qtype} (QT_fp16, QT_8bit, QT_8bit_uniform)")
+
+
+def _parse_sq(r: "_Reader") -> dict:
+    """IndexScalarQuantizer after its fourcc -> {kind "sq", d, ntotal, qtype, metric, is_trained,
+    code_size, trained f32[...], codes u8 [ntotal][code_size]}."""
+    d, ntotal, is_trained, metric = r.header()
+    qtype = r.fmt("i")
+    rangestat = r.fmt("i")
+    r.fmt("f")  # rangestat_arg
+    sd = r.fmt("Q")
+    code_size = r.fmt("Q")
+    trained = r.vector(np.float32)
+    codes = r.vector(np.uint8)
+    cs, nt = sq_shape(qtype, d)
+    if rangestat != 0:
+        raise RuntimeError("only the RS_minmax range statistic is supported")
+    if sd != d or code_size != cs or (is_trained and trained.size != nt):
+        raise RuntimeError("scalar quantizer shape does not match the index")
+    if codes.size != ntotal * cs:
+        raise RuntimeError("IndexScalarQuantizer codes do not match ntotal")
+    return {"kind": "sq", "d": d, "ntotal": ntotal, "qtype": qtype, "metric": metric, "is_trained": is_trained,
+            "code_size": cs, "trained": trained, "codes": codes.reshape(ntotal, cs)}
+
+
+def serialize_sq(d, qtype, metric, trained, codes, is_trained=True) -> bytes:
+    """The inverse of parse_index for kind "sq": codes uint8 [ntotal][code_size].
+    Unpinned against Faiss, like the other layouts (see the module docstring)."""
+    cs, _ = sq_shape(qtype, d)
+    codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    return b"".join([FOURCC_SQ, _header(d, codes.size // cs, is_trained, metric),
+                     struct.pack("<iifQQ", qtype, 0, 0.0, d, cs),
+                     _vector(np.ascontiguousarray(trained, np.float32).reshape(-1)), _vector(codes)])
 
 
 def _parse_linear(r: _Reader) -> dict:

@@ -16,6 +16,8 @@ The surface mirrors what Chameleon's callers use on ``faiss`` (SURVEY.md
   PQFaissSearch, plain or behind ``IndexPreTransform(OPQMatrix, ...)``);
 * ``IndexIVFFlat(quantizer, d, nlist, metric)`` (``bench_gpu_1bn.py:575-578``
   index keys ending in ``,Flat``; ``compute_ground_truth.py:311`` "IVF1,Flat");
+* ``IndexScalarQuantizer(d, qtype, metric)`` and the ``ScalarQuantizer.QT_*`` constants
+  (beir ``faiss_search.py:415-459`` SQFaissSearch: "QT_fp16"; "QT_8bit" by name);
 * ``IndexFlatL2`` (the coarse quantizer; exact search on the GPU);
 * ``index_factory``, ``ParameterSpace``, ``read_index / write_index``,
   ``swig_ptr``, ``vector_to_array``, ``get_num_gpus``.
@@ -989,6 +991,179 @@ class IndexIVFFlat:
                                                         ctypes.c_void_p(self._stream(x, stream))))
 
 
+class ScalarQuantizer:
+    """faiss.ScalarQuantizer: the QuantizerType values (beir faiss_search.py:423 looks the
+    type up by name with getattr), and the ``index.sq`` view of an IndexScalarQuantizer."""
+
+    QT_8bit = 0
+    QT_4bit = 1
+    QT_8bit_uniform = 2
+    QT_4bit_uniform = 3
+    QT_fp16 = 4
+    QT_8bit_direct = 5
+    QT_6bit = 6
+
+    def __init__(self, owner):
+        self._owner = owner
+        self.qtype = owner.qtype
+        self.d = owner.d
+        self.code_size = owner.code_size
+
+    @property
+    def trained(self):
+        """float32: [vmin (d), vdiff (d)] (QT_8bit), [vmin, vdiff] (QT_8bit_uniform), empty (QT_fp16)."""
+        return self._owner._trained()
+
+
+_SQ_NAMES = {v: n for n, v in vars(ScalarQuantizer).items() if n.startswith("QT_")}
+
+
+class IndexScalarQuantizer:
+    """faiss.IndexScalarQuantizer(d, qtype, metric) for QT_fp16, QT_8bit and QT_8bit_uniform
+    (beir faiss_search.py:415-459 SQFaissSearch): every code is decoded and compared with
+    every query in one fused scan.  Labels are positions: there is no id map, as in Faiss."""
+
+    def __init__(self, d, qtype, metric=METRIC_L2, device=None):
+        self.d = int(d)
+        self.qtype = int(qtype)
+        self.metric_type = metric
+        self.device = _default_device() if device is None else int(device)
+        self.verbose = False
+        h = _lib.c_handle()
+        _lib.check(_lib.load().ivfpq_sq_create(self.d, self.qtype, metric, self.device, ctypes.byref(h)))
+        self._h = h
+        cs = ctypes.c_int()
+        _lib.check(_lib.load().ivfpq_sq_get_dims(h, None, None, None, ctypes.byref(cs)))
+        self.code_size = cs.value
+        self.sq = ScalarQuantizer(self)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ivfpq_sq_free(h)
+            self._h = None
+
+    @property
+    def ntotal(self):
+        return int(_lib.load().ivfpq_sq_ntotal(self._h))
+
+    @property
+    def is_trained(self):
+        return bool(_lib.load().ivfpq_sq_is_trained(self._h))
+
+    def sa_code_size(self):
+        return self.code_size
+
+    def _trained(self):
+        if not self.is_trained:
+            return np.zeros(0, np.float32)
+        n = ctypes.c_int64()
+        _lib.check(_lib.load().ivfpq_sq_get_trained(self._h, None, ctypes.byref(n)))
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            _lib.check(_lib.load().ivfpq_sq_get_trained(self._h, _ptr(out, _lib.c_f32p), None))
+        return out
+
+    def _codes(self, i0, n):
+        out = np.empty((n, self.code_size), np.uint8)
+        _lib.check(_lib.load().ivfpq_sq_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
+        return out
+
+    @property
+    def codes(self):
+        """uint8 [ntotal * code_size] (faiss.vector_to_array(index.codes))."""
+        return self._codes(0, self.ntotal).reshape(-1)
+
+    # ----------------------------------------------------------- build path
+    def train(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_sq_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
+
+    def set_trained(self, trained):
+        """Install ``sq.trained`` (see ScalarQuantizer.trained)."""
+        t = np.ascontiguousarray(trained, np.float32).reshape(-1)
+        _lib.check(_lib.load().ivfpq_sq_set_trained(self._h, _ptr(t, _lib.c_f32p), t.size))
+
+    def add(self, x):
+        x = _f32(x, self.d)
+        _lib.check(_lib.load().ivfpq_sq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
+
+    def add_codes(self, codes):
+        """Append precomputed codes uint8 [n][code_size]."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        if codes.size % self.code_size:
+            raise RuntimeError(f"codes must hold whole rows of {self.code_size} bytes")
+        codes = codes.reshape(-1, self.code_size)
+        _lib.check(_lib.load().ivfpq_sq_add_codes(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p)))
+
+    def reset(self):
+        _lib.check(_lib.load().ivfpq_sq_reset(self._h))
+
+    def sa_encode(self, x):
+        """float32 [n][d] -> uint8 [n][code_size], encoded on the GPU."""
+        x = _f32(x, self.d)
+        out = np.empty((x.shape[0], self.code_size), np.uint8)
+        _lib.check(_lib.load().ivfpq_sq_encode(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(out, _lib.c_u8p)))
+        return out
+
+    def sa_decode(self, codes):
+        """uint8 [n][code_size] -> float32 [n][d], decoded on the GPU."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        if codes.size % self.code_size:
+            raise RuntimeError(f"codes must hold whole rows of {self.code_size} bytes")
+        codes = codes.reshape(-1, self.code_size)
+        out = np.empty((codes.shape[0], self.d), np.float32)
+        _lib.check(_lib.load().ivfpq_sq_decode(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p),
+                                               _ptr(out, _lib.c_f32p)))
+        return out
+
+    def reconstruct_n(self, i0, n):
+        return self.sa_decode(self._codes(i0, n))
+
+    def reconstruct(self, i):
+        return self.reconstruct_n(i, 1)[0]
+
+    # ------------------------------------------------------------ search path
+    _check_k = IndexIVFPQ._check_k
+    _check_dev = IndexIVFPQ._check_dev
+    _dev_outputs = IndexIVFPQ._dev_outputs
+    _stream = IndexIVFPQ._stream
+
+    def search(self, x, k):
+        x = _f32(x, self.d)
+        self._check_k(k)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _lib.check(_lib.load().ivfpq_sq_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
+                                               _ptr(I, _lib.c_i64p)))
+        return D, I
+
+    def search_device(self, x, k, D=None, I=None, stream=None):
+        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
+        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
+        import torch
+
+        self._check_k(k)
+        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
+        D, I = self._dev_outputs(x, k, D, I)
+        _lib.check(_lib.load().ivfpq_sq_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
+                                                      I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+    def add_device(self, x, stream=None):
+        """add with the vectors already in HBM; returns once the codes are in place."""
+        import torch
+
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.float32, (n, self.d))
+        _lib.check(_lib.load().ivfpq_sq_add_device(self._h, n, x.data_ptr(),
+                                                   ctypes.c_void_p(self._stream(x, stream))))
+
+
 def decode_pq(codebook, codes):
     """ProductQuantizer::decode: codebook [M][256][dsub], codes uint8 [n][M] -> float32 [n][M * dsub]."""
     M, _, dsub = codebook.shape
@@ -1023,6 +1198,8 @@ def merge_topk_device(Ds, Is, metric=METRIC_L2, stream=None):
 _PQ_FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?PQ(\d+)(?:x(\d+))?$")
 _FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x(\d+))?$")
 _IVFFLAT_FACTORY_RE = re.compile(r"^IVF(\d+),Flat$")
+_SQ_FACTORY_RE = re.compile(r"^SQ(\w+)$")
+_SQ_FACTORY_TYPES = {"8": ScalarQuantizer.QT_8bit, "fp16": ScalarQuantizer.QT_fp16}
 
 
 def parse_factory(key):
@@ -1057,14 +1234,28 @@ def parse_ivfflat_factory(key):
     return int(m.group(1)) if m else None
 
 
+def parse_sq_factory(key):
+    """'SQ8' / 'SQfp16' -> the quantizer type; None for a key that does not start a scalar
+    quantizer; any other 'SQ<x>' (Faiss also has SQ4 and SQ6) raises, naming the key."""
+    m = _SQ_FACTORY_RE.match(key.replace(" ", ""))
+    if not m:
+        return None
+    if m.group(1) not in _SQ_FACTORY_TYPES:
+        raise RuntimeError(f"index_factory: unsupported scalar quantizer key {key!r} (supported: 'SQ8', 'SQfp16')")
+    return _SQ_FACTORY_TYPES[m.group(1)]
+
+
 def index_factory(d, key, metric=METRIC_L2, device=None):
     """faiss.index_factory(d, "IVF1024,PQ16") (bench_polysemous_1bn.py:272), the
     OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), the flat
     "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
     "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
-    truth of compute_ground_truth.py:311)."""
+    truth of compute_ground_truth.py:311), and the flat scalar quantizers "SQ8" / "SQfp16"."""
     from .transform import IndexPreTransform, OPQMatrix
 
+    qtype = parse_sq_factory(key)
+    if qtype is not None:
+        return IndexScalarQuantizer(d, qtype, metric, device)
     nlist = parse_ivfflat_factory(key)
     if nlist is not None:
         return IndexIVFFlat(None, d, nlist, metric, device)
@@ -1124,13 +1315,22 @@ def _ivfflat_bytes(index):
     return faiss_io.serialize_ivfflat(index.d, index.nlist, index.nprobe, index.metric_type, index.centroids(), lists)
 
 
+def _sq_bytes(index):
+    if not index.is_trained:
+        raise RuntimeError("IndexScalarQuantizer is written once trained")
+    return faiss_io.serialize_sq(index.d, index.qtype, index.metric_type, index.sq.trained,
+                                 index._codes(0, index.ntotal))
+
+
 def _sub_bytes(index):
+    if isinstance(index, IndexScalarQuantizer):
+        return _sq_bytes(index)
     return _pq_bytes(index) if isinstance(index, IndexPQ) else _ivfpq_bytes(index)
 
 
 def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
-    IndexIVFFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
+    IndexIVFFlat / IndexScalarQuantizer / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform
 
@@ -1144,6 +1344,10 @@ def write_index(index, path, fmt="faiss"):
         if fmt != "faiss":
             raise RuntimeError("IndexPQ is written in the Faiss layout")
         buf = _pq_bytes(index)
+    elif isinstance(index, IndexScalarQuantizer):
+        if fmt != "faiss":
+            raise RuntimeError("IndexScalarQuantizer is written in the Faiss layout")
+        buf = _sq_bytes(index)
     elif isinstance(index, IndexIVFFlat):
         if fmt != "faiss":
             raise RuntimeError("IndexIVFFlat is written in the Faiss layout")
@@ -1194,14 +1398,25 @@ def _ivfflat_from_dict(z, device):
     return idx
 
 
+def _sq_from_dict(z, device):
+    idx = IndexScalarQuantizer(z["d"], z["qtype"], z["metric"], device)
+    if z["is_trained"]:
+        idx.set_trained(z["trained"])
+        if z["ntotal"]:
+            idx.add_codes(z["codes"])
+    return idx
+
+
 def _index_from_dict(z, device):
     if z["kind"] == "ivfflat":
         return _ivfflat_from_dict(z, device)
+    if z["kind"] == "sq":
+        return _sq_from_dict(z, device)
     return _pq_from_dict(z, device) if z["kind"] == "pq" else _ivfpq_from_dict(z, device)
 
 
 def read_index(path, device=None):
-    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexPreTransform ("IxPT")
+    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexScalarQuantizer ("IxSQ") / IndexPreTransform ("IxPT")
     file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
     if faiss_io.is_faiss_file(path):

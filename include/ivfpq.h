@@ -327,6 +327,62 @@ int ivfpq_ivfflat_get_list_sizes(ivfpq_ivfflat_index* h, int64_t* out);    /* [n
  * ids int64 [size] (either nullable), copied from the device image. */
 int ivfpq_ivfflat_get_list(ivfpq_ivfflat_index* h, int list, float* vectors, int64_t* ids);
 
+/* ---- flat scalar quantizer: faiss.IndexScalarQuantizer(d, qtype, metric) -----------
+ * (beir faiss_search.py:415-459 SQFaissSearch with "QT_fp16"; HNSWSQFaissSearch names
+ * "QT_8bit").  No coarse quantizer and no id map: every code is scanned for every query
+ * and the label of a code is its position.  Encode and decode are Faiss's scalar-build
+ * formulas, every operation one fp32 rounding:
+ *   QT_fp16          code = (half)x, round to nearest even;  y = (float)code
+ *   QT_8bit          xi = vdiff[j] != 0 ? (x - vmin[j]) / vdiff[j] : 0, clamped to [0, 1];
+ *                    code = (uint8)(int)(255.f * xi);
+ *                    y = vmin[j] + (((float)code + 0.5f) / 255.0f) * vdiff[j]
+ *   QT_8bit_uniform  the same with one (vmin, vdiff) pair for all dimensions
+ * Training is RS_minmax with rangestat_arg = 0: vmin = the minimum, vdiff = the maximum
+ * minus it, per dimension or over all entries; QT_fp16 needs none.  A distance is
+ * fvec_L2sqr / fvec_inner_product in Faiss's AVX order over the decoded vector, so a
+ * search equals "IVF1,Flat" over the decoded vectors.  The other quantizer types are
+ * rejected by name.  d must be a multiple of 4 in [4, 2048]; k <= 1024; at most
+ * 2^31 - 2 codes.  Same conventions, errors and locking as above (one mutex per
+ * handle); device calls of one handle on different streams run one after the other. */
+typedef struct ivfpq_sq_index ivfpq_sq_index;
+
+/* faiss.ScalarQuantizer.QuantizerType */
+#define IVFPQ_SQ_8BIT 0
+#define IVFPQ_SQ_4BIT 1
+#define IVFPQ_SQ_8BIT_UNIFORM 2
+#define IVFPQ_SQ_4BIT_UNIFORM 3
+#define IVFPQ_SQ_FP16 4
+#define IVFPQ_SQ_8BIT_DIRECT 5
+#define IVFPQ_SQ_6BIT 6
+
+int ivfpq_sq_create(int d, int qtype, int metric, int device, ivfpq_sq_index** out);
+int ivfpq_sq_free(ivfpq_sq_index* h);
+/* Index.train(x): the minimum and maximum on the GPU (exact, so equal to any other order's). */
+int ivfpq_sq_train(ivfpq_sq_index* h, int64_t n, const float* x);
+/* Install sq.trained: [vmin (d), vdiff (d)] (QT_8bit), [vmin, vdiff] (QT_8bit_uniform), nothing (QT_fp16). */
+int ivfpq_sq_set_trained(ivfpq_sq_index* h, const float* trained, int64_t count);
+/* Index.add(x): encoded on the GPU and appended to the device code image, which grows geometrically. */
+int ivfpq_sq_add(ivfpq_sq_index* h, int64_t n, const float* x);
+/* The same with x in HBM, on `stream` (hipStream_t, NULL = default); returns when the codes are in place. */
+int ivfpq_sq_add_device(ivfpq_sq_index* h, int64_t n, const float* x, void* stream);
+/* Append precomputed codes uint8 [n][code_size] (e.g. from a loaded index file). */
+int ivfpq_sq_add_codes(ivfpq_sq_index* h, int64_t n, const uint8_t* codes);
+/* Index.reset(): drop the codes, keep the trained parameters. */
+int ivfpq_sq_reset(ivfpq_sq_index* h);
+/* Index.search(x, k) -> (D, I), host buffers / device pointers on `stream`. */
+int ivfpq_sq_search(ivfpq_sq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I);
+int ivfpq_sq_search_device(ivfpq_sq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I, void* stream);
+int64_t ivfpq_sq_ntotal(const ivfpq_sq_index* h);
+int ivfpq_sq_is_trained(const ivfpq_sq_index* h);
+int ivfpq_sq_get_dims(const ivfpq_sq_index* h, int* d, int* qtype, int* metric, int* code_size);
+/* sq.trained: *count = its length; out (nullable) receives the values */
+int ivfpq_sq_get_trained(const ivfpq_sq_index* h, float* out, int64_t* count);
+/* codes [i0, i0 + n) of the image, uint8 [n][code_size] (IndexScalarQuantizer.codes) */
+int ivfpq_sq_get_codes(ivfpq_sq_index* h, int64_t i0, int64_t n, uint8_t* out);
+/* Index.sa_encode / sa_decode: x float32 [n][d] <-> codes uint8 [n][code_size], host buffers */
+int ivfpq_sq_encode(ivfpq_sq_index* h, int64_t n, const float* x, uint8_t* codes);
+int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x);
+
 #ifdef __cplusplus
 }
 #endif

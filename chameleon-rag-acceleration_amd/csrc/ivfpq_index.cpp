@@ -32,6 +32,7 @@
 #include "pq_flat.h"
 #include "ivf_flat.h"
 #include "sq_scan.h"
+#include "binary_flat.h"
 
 using namespace chivf;
 
@@ -3147,6 +3148,280 @@ int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     h->decode_host(n, codes, x);
+  });
+}
+
+}  // extern "C"
+
+// ============================================================ flat binary codes (IndexBinaryFlat)
+// faiss.IndexBinaryFlat: uint8 codes of d bits, every code compared with every query by
+// Hamming distance and the k smallest (distance, label) selected by counting
+// (binary_flat.hip).  The codes live in one device image [ntotal][stride] (rows padded with
+// zero bytes to whole loads) that grows geometrically; the label of a code is its position.
+// Device calls on different streams are ordered one after the other (one workspace per handle).
+struct ivfpq_bin_index {
+  int d = 0, code_size = 0, stride = 0, device = 0;
+  int64_t ntotal = 0, cap = 0;  // codes in the image, rows allocated
+  DevBuf d_codes;
+  DevBuf w_x, w_D, w_I, p_qw, p_hist, p_T, p_quota;
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;  // recorded after every device call, on done_stream
+  hipStream_t done_stream = nullptr;
+  bool done_pending = false;
+  std::mutex mu;
+
+  ~ivfpq_bin_index() {
+    if (done) (void)hipEventDestroy(done);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+
+  void order_after(hipStream_t s) {
+    if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
+  }
+  void mark_done(hipStream_t s) {
+    HIPCHECK(hipEventRecord(done, s));
+    done_stream = s;
+    done_pending = true;
+  }
+  void quiesce() {
+    if (done_pending) HIPCHECK(hipEventSynchronize(done));
+    done_pending = false;
+  }
+
+  // room for n more codes: the image doubles (at least) when it is full
+  void reserve(int64_t n, hipStream_t s) {
+    require(ntotal + n < (int64_t)INT32_MAX, "IndexBinaryFlat holds at most 2^31 - 2 codes");
+    if (ntotal + n <= cap) return;
+    quiesce();
+    const int64_t ncap = std::max<int64_t>({ntotal + n, 2 * cap, 1024});
+    const size_t nbytes = (size_t)ncap * stride;
+    void* np = nullptr;
+    HIPCHECK(hipMalloc(&np, nbytes));
+    if (ntotal) {
+      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * stride, hipMemcpyDeviceToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) {
+        (void)hipFree(np);
+        HIPCHECK(e);
+      }
+    }
+    d_codes.release();
+    d_codes.p = np;
+    d_codes.bytes = nbytes;
+    cap = ncap;
+  }
+
+  // pad n device-resident codes [n][code_size] behind the image; returns when they are in place
+  void add_dev(int64_t n, const uint8_t* xd, hipStream_t s) {
+    reserve(n, s);
+    order_after(s);
+    launch_bin_pad_rows(xd, n, code_size, stride, d_codes.as<uint32_t>() + (size_t)ntotal * (stride / 4), s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    ntotal += n;
+  }
+
+  void add_host(int64_t n, const uint8_t* x) {
+    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / code_size));
+    quiesce();
+    w_x.ensure((size_t)rows * code_size);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t c = std::min(rows, n - r0);
+      HIPCHECK(hipMemcpyAsync(w_x.p, x + r0 * code_size, (size_t)c * code_size, hipMemcpyHostToDevice, stream));
+      add_dev(c, w_x.as<uint8_t>(), stream);
+    }
+  }
+
+  // n device-resident queries -> D, I (device), all on s
+  void search_dev(int64_t n, const uint8_t* xd, int k, int32_t* D, int64_t* I, hipStream_t s) {
+    if (n == 0) return;
+    order_after(s);
+    if (ntotal == 0) {
+      launch_bin_fill_empty(D, I, n * k, s);
+      HIPCHECK(hipGetLastError());
+      mark_done(s);
+      return;
+    }
+    const BinPlan pl = bin_plan(d, ntotal, n);
+    const int64_t qc = std::min(pl.qc, n);
+    const int64_t nblocks = (qc + pl.QB - 1) / pl.QB;
+    p_qw.ensure((size_t)nblocks * pl.QB * pl.stride);
+    p_hist.ensure(sizeof(uint32_t) * (size_t)qc * pl.Sg * (d + 1));
+    p_T.ensure(sizeof(int32_t) * qc);
+    p_quota.ensure(sizeof(uint32_t) * (size_t)qc * pl.Sg);
+    for (int64_t q0 = 0; q0 < n; q0 += qc) {
+      BinSearchArgs a;
+      a.x = xd + q0 * code_size;
+      a.nq = std::min(qc, n - q0);
+      a.d = d;
+      a.codes = d_codes.as<uint32_t>();
+      a.nb = ntotal;
+      a.k = k;
+      a.qw = p_qw.as<uint32_t>();
+      a.hist = p_hist.as<uint32_t>();
+      a.T = p_T.as<int32_t>();
+      a.quota = p_quota.as<uint32_t>();
+      a.D = D + q0 * k;
+      a.I = I + q0 * k;
+      launch_bin_search(a, pl, s);
+      HIPCHECK(hipGetLastError());
+    }
+    mark_done(s);
+  }
+
+  void search_host(int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I) {
+    if (n == 0) return;
+    quiesce();
+    w_x.ensure((size_t)n * code_size);
+    w_D.ensure(sizeof(int32_t) * n * k);
+    w_I.ensure(sizeof(int64_t) * n * k);
+    HIPCHECK(hipMemcpyAsync(w_x.p, x, (size_t)n * code_size, hipMemcpyHostToDevice, stream));
+    search_dev(n, w_x.as<uint8_t>(), k, w_D.as<int32_t>(), w_I.as<int64_t>(), stream);
+    HIPCHECK(hipMemcpyAsync(D, w_D.p, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipMemcpyAsync(I, w_I.p, sizeof(int64_t) * n * k, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+};
+
+namespace {
+void check_bin(const ivfpq_bin_index* h) { require(h != nullptr, "null index handle"); }
+void check_bin_d(int d) {
+  require(d >= 8 && d <= kBinMaxD && d % 8 == 0,
+          "IndexBinaryFlat: d must be a multiple of 8 in [8, 2048] (d = " + std::to_string(d) + ")");
+}
+void check_bin_search(int64_t n, const void* x, int k, const void* D, const void* I) {
+  require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+  require(n >= 0, "negative query count");
+  require(n == 0 || (x && D && I), "null x / D / I");
+}
+}  // namespace
+
+extern "C" {
+
+int ivfpq_bin_create(int d, int device, ivfpq_bin_index** out) {
+  return guarded([&] {
+    require(out != nullptr, "null output pointer");
+    check_bin_d(d);
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    require(device >= 0 && device < ndev, "device ordinal out of range");
+    DeviceGuard g(device);
+    auto h = std::make_unique<ivfpq_bin_index>();
+    h->d = d;
+    h->code_size = d / 8;
+    h->stride = bin_stride(h->code_size);
+    h->device = device;
+    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    *out = h.release();
+  });
+}
+
+int ivfpq_bin_free(ivfpq_bin_index* h) {
+  return guarded([&] {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->quiesce();
+    delete h;
+  });
+}
+
+int ivfpq_bin_reset(ivfpq_bin_index* h) {
+  return guarded([&] {
+    check_bin(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->quiesce();
+    h->d_codes.release();
+    h->ntotal = h->cap = 0;
+  });
+}
+
+int ivfpq_bin_add(ivfpq_bin_index* h, int64_t n, const uint8_t* x) {
+  return guarded([&] {
+    check_bin(h);
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->add_host(n, x);
+  });
+}
+
+int ivfpq_bin_add_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, void* stream) {
+  return guarded([&] {
+    check_bin(h);
+    if (n <= 0) return;
+    require(x != nullptr, "null x");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->add_dev(n, x, (hipStream_t)stream);
+  });
+}
+
+int ivfpq_bin_search(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I) {
+  return guarded([&] {
+    check_bin_search(n, x, k, D, I);
+    check_bin(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->search_host(n, x, k, D, I);
+  });
+}
+
+int ivfpq_bin_search_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I,
+                            void* stream) {
+  return guarded([&] {
+    check_bin_search(n, x, k, D, I);
+    check_bin(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    h->search_dev(n, x, k, D, I, (hipStream_t)stream);
+  });
+}
+
+int64_t ivfpq_bin_ntotal(const ivfpq_bin_index* h) { return h ? h->ntotal : -1; }
+
+int ivfpq_bin_get_dims(const ivfpq_bin_index* h, int* d, int* code_size) {
+  return guarded([&] {
+    check_bin(h);
+    if (d) *d = h->d;
+    if (code_size) *code_size = h->code_size;
+  });
+}
+
+int ivfpq_bin_get_codes(ivfpq_bin_index* h, int64_t i0, int64_t n, uint8_t* out) {
+  return guarded([&] {
+    check_bin(h);
+    std::lock_guard<std::mutex> lk(h->mu);
+    require(i0 >= 0 && n >= 0 && i0 + n <= h->ntotal, "code range outside [0, ntotal)");
+    if (n == 0) return;
+    require(out != nullptr, "null output pointer");
+    DeviceGuard g(h->device);
+    h->quiesce();
+    const uint8_t* src = h->d_codes.as<uint8_t>() + (size_t)i0 * h->stride;
+    if (h->stride == h->code_size)
+      HIPCHECK(hipMemcpyAsync(out, src, (size_t)n * h->code_size, hipMemcpyDeviceToHost, h->stream));
+    else  // the rows without their pad bytes
+      HIPCHECK(hipMemcpy2DAsync(out, h->code_size, src, h->stride, h->code_size, n, hipMemcpyDeviceToHost,
+                                h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  });
+}
+
+int ivfpq_bin_get_plan(int d, int64_t ntotal, int64_t nq, int k, int* stride, int* query_block, int* segments,
+                       int64_t* segment_rows, int64_t* query_chunk) {
+  return guarded([&] {
+    check_bin_d(d);
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(ntotal >= 0 && ntotal < (int64_t)INT32_MAX && nq >= 0, "ntotal / nq out of range");
+    const BinPlan pl = bin_plan(d, ntotal, nq);
+    if (stride) *stride = pl.stride;
+    if (query_block) *query_block = pl.QB;
+    if (segments) *segments = pl.Sg;
+    if (segment_rows) *segment_rows = pl.seg_rows;
+    if (query_chunk) *query_chunk = pl.qc;
   });
 }
 

@@ -10,6 +10,7 @@ from .index import (  # noqa: F401
     MAX_K,
     METRIC_INNER_PRODUCT,
     METRIC_L2,
+    IndexBinaryFlat,
     IndexFlatIP,
     IndexFlatL2,
     IndexIVFFlat,
@@ -21,13 +22,16 @@ from .index import (  # noqa: F401
     downcast_index,
     extract_index_ivf,
     get_num_gpus,
+    index_binary_factory,
     index_factory,
     merge_topk_device,
     overlap_built,
     read_index,
+    read_index_binary,
     swig_ptr,
     vector_to_array,
     write_index,
+    write_index_binary,
 )
 from .transform import (  # noqa: F401
     IndexPreTransform,

@@ -21,6 +21,7 @@ _lib = None
 c_f32p = ctypes.POINTER(ctypes.c_float)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
+c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_handle = ctypes.c_void_p
 
 # name -> (restype, argtypes); mirrors include/ivfpq.h one to one, plus the
@@ -159,6 +160,21 @@ SIGNATURES = {
     "ivfpq_sq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
     "ivfpq_sq_encode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_u8p]),
     "ivfpq_sq_decode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, c_f32p]),
+    # flat binary codes (IndexBinaryFlat)
+    "ivfpq_bin_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_handle)]),
+    "ivfpq_bin_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_bin_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_bin_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
+    "ivfpq_bin_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_bin_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, ctypes.c_int, c_i32p, c_i64p]),
+    "ivfpq_bin_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_bin_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_bin_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "ivfpq_bin_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
+    "ivfpq_bin_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int), c_i64p, c_i64p]),
 }
 
 

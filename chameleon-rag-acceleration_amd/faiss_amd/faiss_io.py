@@ -49,6 +49,14 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
     "IxPT" may wrap it too.
     Unpinned like the others: no Faiss-written "IxSQ" file exists on the build machine.
 
+    "IBxF"                                   IndexBinaryFlat (beir faiss_search.py BinaryFaissSearch;
+                                             written by write_index_binary, read by read_index_binary)
+      d i32 (bits), code_size i32 (d / 8), ntotal i64, is_trained u8, metric_type i32 (1)
+      xb = u64 count + u8[ntotal * code_size]
+    A binary index has its own header (no dummies) and its own reader: read_index rejects it,
+    read_index_binary rejects the float layouts, each naming the fourcc.
+    Unpinned like the others: no Faiss-written "IBxF" file exists on the build machine.
+
 Parity is unpinned: no Faiss-written file exists in the reference or this image
 (the reference's ``*.index`` files are not shipped), so the tests check a
 hand-assembled byte layout and round trips, not a file from real Faiss.
@@ -64,6 +72,7 @@ FOURCC_PQ = b"IxPq"
 FOURCC_IVFFLAT = b"IwFl"
 FOURCC_SQ = b"IxSQ"
 SQ_QT_8BIT, SQ_QT_8BIT_UNIFORM, SQ_QT_FP16 = 0, 2, 4  # the scalar quantizer types that are read and written
+FOURCC_BINARY_FLAT = b"IBxF"
 FOURCC_FLAT = {0: b"IxFI", 1: b"IxF2"}  # metric_type: 0 = INNER_PRODUCT, 1 = L2
 HEADER_DUMMY = 1 << 20
 
@@ -240,6 +249,42 @@ def serialize_sq(d, qtype, metric, trained, codes, is_trained=True) -> bytes:
     return b"".join([FOURCC_SQ, _header(d, codes.size // cs, is_trained, metric),
                      struct.pack("<iifQQ", qtype, 0, 0.0, d, cs),
                      _vector(np.ascontiguousarray(trained, np.float32).reshape(-1)), _vector(codes)])
+
+
+def parse_index_binary(buf: bytes) -> dict:
+    """Faiss IndexBinaryFlat ("IBxF") bytes -> {kind "binary_flat", d (bits), code_size, ntotal,
+    is_trained, metric, codes u8 [ntotal][code_size]}."""
+    r = _Reader(buf)
+    h = r.fourcc()
+    if h != FOURCC_BINARY_FLAT:
+        raise RuntimeError(f"not a Faiss binary index file (fourcc {h!r}; IndexBinaryFlat {FOURCC_BINARY_FLAT!r} "
+                           "only - float indexes are read with read_index)")
+    d = r.fmt("i")
+    code_size = r.fmt("i")
+    ntotal = r.fmt("q")
+    is_trained = r.fmt("B") != 0
+    metric = r.fmt("i")
+    codes = r.vector(np.uint8)
+    if d <= 0 or d % 8 or code_size != d // 8:
+        raise RuntimeError("IndexBinaryFlat code size does not match d")
+    if ntotal < 0 or codes.size != ntotal * code_size:
+        raise RuntimeError("IndexBinaryFlat xb does not match ntotal")
+    if r.o != len(r.b):
+        raise RuntimeError("trailing bytes after the index")
+    return {"kind": "binary_flat", "d": d, "code_size": code_size, "ntotal": ntotal, "is_trained": is_trained,
+            "metric": metric, "codes": codes.reshape(ntotal, code_size)}
+
+
+def serialize_binary_flat(d, codes) -> bytes:
+    """The inverse of parse_index_binary: d in bits, codes uint8 [ntotal][d / 8].
+    Unpinned against Faiss, like the other layouts (see the module docstring)."""
+    if d <= 0 or d % 8:
+        raise RuntimeError(f"IndexBinaryFlat: d must be a positive multiple of 8, got {d}")
+    cs = d // 8
+    codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    if codes.size % cs:
+        raise RuntimeError(f"codes must hold whole rows of {cs} bytes")
+    return b"".join([FOURCC_BINARY_FLAT, struct.pack("<iiqBi", d, cs, codes.size // cs, 1, 1), _vector(codes)])
 
 
 def _parse_linear(r: _Reader) -> dict:

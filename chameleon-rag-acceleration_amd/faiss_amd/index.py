@@ -18,6 +18,9 @@ The surface mirrors what Chameleon's callers use on ``faiss`` (SURVEY.md
   index keys ending in ``,Flat``; ``compute_ground_truth.py:311`` "IVF1,Flat");
 * ``IndexScalarQuantizer(d, qtype, metric)`` and the ``ScalarQuantizer.QT_*`` constants
   (beir ``faiss_search.py:415-459`` SQFaissSearch: "QT_fp16"; "QT_8bit" by name);
+* ``IndexBinaryFlat(d)`` with ``index_binary_factory``, ``write_index_binary`` and
+  ``read_index_binary`` (beir ``faiss_search.py:134-166`` BinaryFaissSearch through
+  ``faiss_index.py:98-174`` FaissBinaryIndex: Hamming candidates, then a float re-rank);
 * ``IndexFlatL2`` (the coarse quantizer; exact search on the GPU);
 * ``index_factory``, ``ParameterSpace``, ``read_index / write_index``,
   ``swig_ptr``, ``vector_to_array``, ``get_num_gpus``.
@@ -1164,6 +1167,119 @@ class IndexScalarQuantizer:
                                                    ctypes.c_void_p(self._stream(x, stream))))
 
 
+class IndexBinaryFlat:
+    """faiss.IndexBinaryFlat(d): exact Hamming search over uint8 codes of ``d`` bits (beir
+    faiss_search.py BinaryFaissSearch builds ``IndexBinaryFlat(dim * 8)``).  ``search`` returns
+    ``D`` int32 and ``I`` int64: per query the k smallest (hamming, label) pairs ascending, ties
+    by label, padded with (2147483647, -1).  The distances equal Faiss's for either value of
+    ``use_heap``; the labels equal ``use_heap = False`` (hammings_knn_mc, first-seen ids per
+    distance), while Faiss's default heap path may keep other ties at the k-th distance and
+    orders equal distances arbitrarily.  Labels are positions: there is no id map."""
+
+    def __init__(self, d, device=None):
+        self.d = int(d)
+        self.metric_type = METRIC_L2  # as Faiss's IndexBinary
+        self.device = _default_device() if device is None else int(device)
+        self.verbose = False
+        self.use_heap = True          # accepted, no effect: see the class comment
+        self.query_batch_size = 32    # accepted, no effect
+        h = _lib.c_handle()
+        _lib.check(_lib.load().ivfpq_bin_create(self.d, self.device, ctypes.byref(h)))
+        self._h = h
+        self.code_size = self.d // 8
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ivfpq_bin_free(h)
+            self._h = None
+
+    @property
+    def ntotal(self):
+        return int(_lib.load().ivfpq_bin_ntotal(self._h))
+
+    @property
+    def is_trained(self):
+        return True
+
+    def _u8(self, x, name="x"):
+        a = np.ascontiguousarray(x)
+        if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != self.code_size:
+            raise RuntimeError(f"{name} must be a uint8 matrix with {self.code_size} columns, got "
+                               f"{a.dtype} {a.shape}")
+        return a
+
+    def _codes(self, i0, n):
+        out = np.empty((n, self.code_size), np.uint8)
+        _lib.check(_lib.load().ivfpq_bin_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
+        return out
+
+    @property
+    def xb(self):
+        """uint8 [ntotal * code_size] (faiss.vector_to_array(index.xb))."""
+        return self._codes(0, self.ntotal).reshape(-1)
+
+    def train(self, x):
+        pass
+
+    def add(self, x):
+        x = self._u8(x)
+        _lib.check(_lib.load().ivfpq_bin_add(self._h, x.shape[0], _ptr(x, _lib.c_u8p)))
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss IndexBinary::add_with_ids
+
+    def reset(self):
+        _lib.check(_lib.load().ivfpq_bin_reset(self._h))
+
+    def reconstruct_n(self, i0, n):
+        return self._codes(i0, n)
+
+    def reconstruct(self, i):
+        return self._codes(i, 1)[0]
+
+    _check_k = IndexIVFPQ._check_k
+    _check_dev = IndexIVFPQ._check_dev
+    _stream = IndexIVFPQ._stream
+
+    def search(self, x, k):
+        x = self._u8(x)
+        self._check_k(k)
+        n = x.shape[0]
+        D = np.empty((n, k), np.int32)
+        I = np.empty((n, k), np.int64)
+        _lib.check(_lib.load().ivfpq_bin_search(self._h, n, _ptr(x, _lib.c_u8p), int(k), _ptr(D, _lib.c_i32p),
+                                                _ptr(I, _lib.c_i64p)))
+        return D, I
+
+    def search_device(self, x, k, D=None, I=None, stream=None):
+        """Search with the queries resident in HBM (torch uint8 CUDA tensor [n, code_size]);
+        returns torch (D int32, I int64), launched on ``stream`` (default: torch's current stream)."""
+        import torch
+
+        self._check_k(k)
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.uint8, (n, self.code_size))
+        if D is None:
+            D = torch.empty((n, k), dtype=torch.int32, device=x.device)
+        if I is None:
+            I = torch.empty((n, k), dtype=torch.int64, device=x.device)
+        self._check_dev(D, "D", torch.int32, (n, k))
+        self._check_dev(I, "I", torch.int64, (n, k))
+        _lib.check(_lib.load().ivfpq_bin_search_device(self._h, n, x.data_ptr(), int(k), D.data_ptr(), I.data_ptr(),
+                                                       ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+    def add_device(self, x, stream=None):
+        """add with the codes already in HBM; returns once they are in place."""
+        import torch
+
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.uint8, (n, self.code_size))
+        _lib.check(_lib.load().ivfpq_bin_add_device(self._h, n, x.data_ptr(),
+                                                    ctypes.c_void_p(self._stream(x, stream))))
+
+
 def decode_pq(codebook, codes):
     """ProductQuantizer::decode: codebook [M][256][dsub], codes uint8 [n][M] -> float32 [n][M * dsub]."""
     M, _, dsub = codebook.shape
@@ -1243,6 +1359,19 @@ def parse_sq_factory(key):
     if m.group(1) not in _SQ_FACTORY_TYPES:
         raise RuntimeError(f"index_factory: unsupported scalar quantizer key {key!r} (supported: 'SQ8', 'SQfp16')")
     return _SQ_FACTORY_TYPES[m.group(1)]
+
+
+def parse_binary_factory(key):
+    """'BFlat' -> True; any other key raises, naming it (Faiss also has BIVF, BHNSW, BHash)."""
+    if key.replace(" ", "") != "BFlat":
+        raise RuntimeError(f"index_binary_factory: unsupported key {key!r} (supported: 'BFlat')")
+    return True
+
+
+def index_binary_factory(d, key, device=None):
+    """faiss.index_binary_factory(d, "BFlat"): d in bits."""
+    parse_binary_factory(key)
+    return IndexBinaryFlat(d, device)
 
 
 def index_factory(d, key, metric=METRIC_L2, device=None):
@@ -1419,6 +1548,10 @@ def read_index(path, device=None):
     """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexScalarQuantizer ("IxSQ") / IndexPreTransform ("IxPT")
     file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
+    with open(path, "rb") as f:
+        if f.read(4) == faiss_io.FOURCC_BINARY_FLAT:
+            raise RuntimeError(f"{path}: fourcc {faiss_io.FOURCC_BINARY_FLAT!r} is a binary index "
+                               "(IndexBinaryFlat): read it with read_index_binary")
     if faiss_io.is_faiss_file(path):
         with open(path, "rb") as f:
             z = faiss_io.parse_index(f.read())
@@ -1436,4 +1569,22 @@ def read_index(path, device=None):
     idx = IndexIVFPQ(None, d, nlist, M, nbits, metric, device, _handle=h)
     if idx.is_trained:
         idx._sync_quantizer()
+    return idx
+
+
+def write_index_binary(index, path):
+    """faiss.write_index_binary: an IndexBinaryFlat in Faiss's "IBxF" layout (faiss_io.py)."""
+    if not isinstance(index, IndexBinaryFlat):
+        raise RuntimeError(f"write_index_binary takes an IndexBinaryFlat, got {type(index).__name__}")
+    with open(path, "wb") as f:
+        f.write(faiss_io.serialize_binary_flat(index.d, index._codes(0, index.ntotal)))
+
+
+def read_index_binary(path, device=None):
+    """faiss.read_index_binary: load an "IBxF" file onto ``device``."""
+    with open(path, "rb") as f:
+        z = faiss_io.parse_index_binary(f.read())
+    idx = IndexBinaryFlat(z["d"], device)
+    if z["ntotal"]:
+        idx.add(z["codes"])
     return idx

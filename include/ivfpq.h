@@ -383,6 +383,43 @@ int ivfpq_sq_get_codes(ivfpq_sq_index* h, int64_t i0, int64_t n, uint8_t* out);
 int ivfpq_sq_encode(ivfpq_sq_index* h, int64_t n, const float* x, uint8_t* codes);
 int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x);
 
+/* ---- flat binary codes: faiss.IndexBinaryFlat(d) -----------------------------------
+ * (beir faiss_search.py BinaryFaissSearch: IndexBinaryFlat(dim * 8), binary_k = 1000
+ * Hamming candidates, then a float re-rank).  d is in bits, a multiple of 8 in [8, 2048];
+ * codes and queries are uint8 [n][d / 8].  Nothing is trained; the label of a code is its
+ * position.  search returns D int32 and I int64 [n][k]: per query the k smallest
+ * (hamming, label) pairs ascending, ties by label, padded with (2147483647, -1) - Faiss's
+ * CMax<int32_t> neutral - where fewer than k codes exist.  Relation to Faiss: the distances
+ * equal Faiss's for either value of use_heap; the labels equal use_heap = false
+ * (hammings_knn_mc, which keeps the first-seen ids per distance); Faiss's default heap path
+ * may keep other ties at the k-th distance and orders equal distances arbitrarily.
+ * 1 <= k <= 1024; at most 2^31 - 2 codes.  The top-k is a counting select in two passes over
+ * the codes (csrc/binary_flat.h).  Same conventions, errors and locking as above (one mutex
+ * per handle); device calls of one handle on different streams run one after the other. */
+typedef struct ivfpq_bin_index ivfpq_bin_index;
+
+int ivfpq_bin_create(int d, int device, ivfpq_bin_index** out);
+int ivfpq_bin_free(ivfpq_bin_index* h);
+/* IndexBinary.reset(): drop the codes. */
+int ivfpq_bin_reset(ivfpq_bin_index* h);
+/* IndexBinary.add(x): appended to the device code image, which grows geometrically. */
+int ivfpq_bin_add(ivfpq_bin_index* h, int64_t n, const uint8_t* x);
+/* The same with x in HBM, on `stream` (hipStream_t, NULL = default); returns when the codes are in place. */
+int ivfpq_bin_add_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, void* stream);
+/* IndexBinary.search(x, k) -> (D, I), host buffers / device pointers on `stream`. */
+int ivfpq_bin_search(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I);
+int ivfpq_bin_search_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I,
+                            void* stream);
+int64_t ivfpq_bin_ntotal(const ivfpq_bin_index* h);
+int ivfpq_bin_get_dims(const ivfpq_bin_index* h, int* d, int* code_size);
+/* codes [i0, i0 + n) without the image's pad bytes, uint8 [n][code_size] (IndexBinaryFlat.xb) */
+int ivfpq_bin_get_codes(ivfpq_bin_index* h, int64_t i0, int64_t n, uint8_t* out);
+/* The plan of a search of nq queries for k results over ntotal codes of d bits (no handle,
+ * no device call): bytes per row of the image, queries per work item, row segments and rows
+ * per segment, queries per chunk of the histogram workspace.  Outputs are nullable. */
+int ivfpq_bin_get_plan(int d, int64_t ntotal, int64_t nq, int k, int* stride, int* query_block, int* segments,
+                       int64_t* segment_rows, int64_t* query_chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,7 +118,10 @@ struct ListPlan {
   uint4* part;
   uint2* partN;      // [nq][nprobe][4] (valid entries, tag) of each partial list (k > 64 writes only those)
   float* pd0;        // [nq][nprobe] the dis0 each planned pair was scanned with (a merge's rescan)
-  int32_t* qdone;    // [nq] k > 64: 1 = merged by k_merge_big (k_merge_probes resets it to 0)
+  // [nq] k > 64, nprobe <= 64: set by k_merge_radix or k_merge_big, whichever ran: 1 = merged there,
+  // 2 = a stale read (counted there); left 0 when the query's ties overflow the kernel's buffer.
+  // k_merge_probes<R> returns at 1, runs its full merge at 0 and 2, and resets the word to 0
+  int32_t* qdone;
   // [nq] running k-th key per query, tagged with the batch: (~epoch) << 32 |
   // order-preserving key bits, lowered by 64-bit atomicMin.  A newer batch's
   // words compare below every older batch's, so no reset store is needed and a

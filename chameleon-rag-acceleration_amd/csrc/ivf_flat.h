@@ -58,7 +58,8 @@ struct IvfFlatArgs {
 // d % 4 == 0, nq * plan.S < 2^31
 void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& plan, hipStream_t s);
 
-// D[i] = FLT_MAX (-FLT_MAX for ip), I[i] = -1: the result of searching an empty index
-void launch_ivfflat_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s);
+// D[i] = FLT_MAX (-FLT_MAX for ip), I[i] = -1: the result of searching an empty index (every
+// float-distance index), and the pad of partial lists no work item writes
+void launch_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s);
 
 }  // namespace chivf

@@ -13,14 +13,18 @@
 //    scalar cache.  Every lane carries Faiss's eight interleaved accumulators per
 //    query from one 32-dimension step to the next, so the sum is tree<>'s whatever d;
 //  * each wave keeps the k best (key, image position) of its rows in registers (the
-//    bitonic wave top-k of ivfpq_kernels.hip, restated in scan_topk.h for int32 positions;
-//    inside one row range position order is label order) and writes them sorted with
+//    wave top-k of scan_topk.h, the one of all three flat scans; inside one row range
+//    position order is label order) and writes them sorted with
 //    their int64 labels; launch_merge_topk, composed in rounds, merges the partial
 //    lists by (key, label).  No distance is written to memory.
 //    Waves that hold k rows lower a per-query bound (their k-th key) that every wave
 //    reads at each tile, so that later work items of a query admit almost nothing.
 //    k <= 64 merges a pass's admitted rows at once; k > 64 queues them in LDS per
 //    (wave, query) and merges 64 at a time, as k_pq_scan does.
+//    The tail of a pass -- distance terms, the fold to a key, admission, drain sites,
+//    the sorted write -- is scan_topk.h's (admission, drain sites and write shared with
+//    k_pq_scan); this file keeps the planning, the fp32 staging and the item numbering.
+//  * launch_fill_empty (the result of an empty index) serves every float-distance index.
 // Compiled with -ffp-contract=off like the rest of the library.
 #include <float.h>
 #include <stdint.h>
@@ -31,7 +35,7 @@
 
 #include "ivf_flat.h"
 #include "ivfpq_kernels.h"
-#include "scan_topk.h"  // the wave top-k, the shared bound, the candidate queue, the merge rounds
+#include "scan_topk.h"  // the wave top-k, the shared bound, the candidate queue, the pass tail, the merge rounds
 
 namespace chivf {
 
@@ -108,8 +112,9 @@ __global__ __launch_bounds__(256) void k_ivfflat_pad(const int32_t* __restrict__
   partI[gid] = -1;
 }
 
-__global__ __launch_bounds__(256) void k_ivfflat_fill_empty(float* __restrict__ D, int64_t* __restrict__ I, int64_t n,
-                                                            float pad) {
+// (pad, -1) over n entries: launch_fill_empty, for every float-distance index
+__global__ __launch_bounds__(256) void k_fill_empty(float* __restrict__ D, int64_t* __restrict__ I, int64_t n,
+                                                    float pad) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= n) return;
   D[gid] = pad;
@@ -123,6 +128,7 @@ constexpr int kDc = 32;             // dimensions per staged step (a multiple of
 constexpr int kRowStride = kDc + 4; // floats per LDS row: 16-byte aligned, and consecutive rows start 4 banks apart
 constexpr int kTile = 256;          // rows per pass: one per thread
 constexpr int kLoads = kTile * kDc / 4 / 256;  // 16-byte loads per thread and step
+constexpr int kQ = kQueue<1>;       // queued candidates per (wave, query): one push per lane and pass
 
 // Persistent over work items: workgroup b takes items b, b + gridDim.x, ...
 // LDS: the 36 KiB tile, plus G KiB of candidate queues per wave when R > 1.
@@ -135,8 +141,8 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
                                                       int k, int S, float* __restrict__ partD, int64_t* __restrict__ partI) {
   __shared__ __attribute__((aligned(16))) float tile[kTile * kRowStride];
   constexpr bool kQueued = R > 1;
-  __shared__ float qd[kQueued ? kIvfFlatWaves * G * kQueue : 1];
-  __shared__ int qi[kQueued ? kIvfFlatWaves * G * kQueue : 1];
+  __shared__ float qd[kQueued ? kIvfFlatWaves * G * kQ : 1];
+  __shared__ int qi[kQueued ? kIvfFlatWaves * G * kQ : 1];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -222,93 +228,26 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
           const f4 y0 = *reinterpret_cast<const f4*>(yrow + j8 * 8);
           const f4 y1 = *reinterpret_cast<const f4*>(yrow + j8 * 8 + 4);
           const float y[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
-#pragma unroll
-          for (int g = 0; g < G; g++) {
-            const float* qp = x + (int64_t)qid[g] * d + c * kDc + j8 * 8;  // wave-uniform
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-              float p;
-              if (KIND == K_IP) {
-                p = qp[j] * y[j];
-              } else {
-                const float t = qp[j] - y[j];
-                p = t * t;
-              }
-              acc[g][j] = acc[g][j] + p;
-            }
-          }
+          accumulate8<KIND>(acc, y, x, d, qid, c * kDc + j8 * 8);
         }
         if (c + 1 < nchunk) continue;
 
-        // the row's last step: fold to four, the 4-wide remainder, two horizontal adds
+        // the row's last step: its key (with the 4-wide remainder), then the admission
         const int64_t rowpos = t0 + tid;
-        const bool valid = rowpos < r1;
         const bool rem = (len & 4) != 0;
         f4 yr = {0.f, 0.f, 0.f, 0.f};
         if (rem) yr = *reinterpret_cast<const f4*>(yrow + n8 * 8);
         const float y[4] = {yr.x, yr.y, yr.z, yr.w};
 #pragma unroll
         for (int g = 0; g < G; g++) {
-          float a4[4];
-#pragma unroll
-          for (int j = 0; j < 4; j++) a4[j] = acc[g][j + 4] + acc[g][j];
-          if (rem) {
-            const float* qp = x + (int64_t)qid[g] * d + c * kDc + n8 * 8;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              float p;
-              if (KIND == K_IP) {
-                p = qp[j] * y[j];
-              } else {
-                const float t = qp[j] - y[j];
-                p = t * t;
-              }
-              a4[j] = a4[j] + p;
-            }
-          }
-          const float h0 = a4[0] + a4[1];
-          const float h1 = a4[2] + a4[3];
-          const float dis = h0 + h1;
-          const float key = KIND == K_IP ? -dis : dis;
-#pragma unroll
-          for (int j = 0; j < 8; j++) acc[g][j] = 0.f;
+          const float key = fold_key<KIND>(acc[g], rem, x + (int64_t)qid[g] * d + c * kDc + n8 * 8, y);
           if (g >= npair) continue;  // uniform
-          // admission against the query's running k-th best
-          const bool pass = valid & lexless(key, (int)rowpos, tk[g].td, tk[g].ti);
-          const uint64_t mask = __ballot(pass);
-          if (!mask) continue;
-          if constexpr (!kQueued) {
-            bulk_merge_rows<R>(tk[g], pass ? key : kInf, pass ? (int)rowpos : kNone, lane);
+          if (admit<R>(tk[g], rowpos < r1, key, (int)rowpos, qn[g], qd + (wave * G + g) * kQ, qi + (wave * G + g) * kQ,
+                       lane))
             tk[g].publish(tau + qid[g], lane);
-          } else {
-            const int before =
-                __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-            if (pass) {
-              const int at = (wave * G + g) * kQueue + qn[g] + before;
-              qd[at] = key;
-              qi[at] = (int)rowpos;
-            }
-            qn[g] += __popcll(mask);
-          }
         }
-        if constexpr (kQueued) {
-          // one drain site per query: full batches of 64 after every pass, the rest after the last
-          const int keep = t0 + kTile < r1 ? 63 : 0;
-          // (spelled out per query: a loop over g around R = 16 merges is past the
-          // compiler's unroll budget, and the top-k arrays would then live in scratch)
-          static_assert(G <= 4, "drain sites are spelled out for up to four queries");
-#define IVFFLAT_DRAIN(g)                                                                                  \
-  if constexpr (G > g) {                                                                                  \
-    while (qn[g] > keep)                                                                                  \
-      drain_queue<R>(tk[g], qn[g], qd + (wave * G + g) * kQueue, qi + (wave * G + g) * kQueue, lane);     \
-    tk[g].publish(tau + qid[g], lane);                                                                    \
-  }
-          IVFFLAT_DRAIN(0);
-          IVFFLAT_DRAIN(1);
-          IVFFLAT_DRAIN(2);
-          IVFFLAT_DRAIN(3);
-#undef IVFFLAT_DRAIN
-        }
+        if constexpr (kQueued)
+          drain_queues<1, true>(tk, qn, t0 + kTile < r1 ? 63 : 0, qd, qi, wave, lane, tau, qid);
       }
     }
 
@@ -317,24 +256,11 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
     for (int g = 0; g < G; g++) {
       if (g >= npair || slot[g] * kIvfFlatWaves + wave >= S) continue;  // (the host's slot bound holds)
       const int64_t base = (((int64_t)slot[g] * kIvfFlatWaves + wave) * nq + qid[g]) * k;
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        const int idx = r * 64 + lane;
-        if (idx < k) {
-          const int pos = tk[g].id[r];
-          const bool none = pos == kNone;
-          const float key = tk[g].d[r];
-          partD[base + idx] = none ? (KIND == K_IP ? -FLT_MAX : FLT_MAX) : (KIND == K_IP ? -key : key);
-          partI[base + idx] = none ? -1 : ids[pos];
-        }
-      }
+      write_sorted<R>(tk[g], k, KIND == K_IP, partD + base, partI + base, lane, [&](int pos) { return ids[pos]; });
     }
   }
 }
 
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-inline int scan_rows_for(int k) { return k <= 64 ? 1 : k <= 256 ? 4 : 16; }
 inline int scan_group_for(int k) { return k <= 64 ? 8 : 4; }
 
 template <int KIND, int G, int R>
@@ -372,9 +298,9 @@ IvfFlatPlan ivfflat_plan(int k, int64_t slots) {
   return p;
 }
 
-void launch_ivfflat_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s) {
+void launch_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_ivfflat_fill_empty, dim3(nblocks(n, 256)), dim3(256), 0, s, D, I, n, ip ? -FLT_MAX : FLT_MAX);
+  hipLaunchKernelGGL(k_fill_empty, dim3(nblocks(n, 256)), dim3(256), 0, s, D, I, n, ip ? -FLT_MAX : FLT_MAX);
 }
 
 void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& p, hipStream_t s) {

@@ -1778,42 +1778,32 @@ int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n,
 
 }  // extern "C"
 
-// ================================================================ flat PQ (IndexPQ)
-// faiss.IndexPQ: no coarse quantizer and no inverted lists -- one product quantizer
-// over the raw vectors, every code scanned for every query (pq_flat.hip).  The codes
-// live in one device image that grows geometrically; the label of a code is its
-// position.  Device calls on different streams are ordered one after the other
-// (one workspace per handle).
+// ================================================================ the flat indexes' code store
+// What IndexPQ, IndexScalarQuantizer and IndexBinaryFlat share: one device image of
+// fixed-size code rows [ntotal][row_bytes] that grows geometrically (with `slack` bytes
+// behind it where the scan reads past a row), the label of a code being its position;
+// the handle's own stream; and the ordering of device calls on different streams one
+// after the other (one workspace per handle).
 namespace {
 
-// queries per chunk of a flat-PQ search: the tables (M KiB per query) within kChunkBytes,
-// the grid's y extent (shared by the handle and ivfpq_pq_debug_plan)
-int64_t pq_query_chunk(int M, int64_t n) {
-  return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
-}
-
-const char* pq_supported_M_text() { return " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)"; }
-
-}  // namespace
-
-struct ivfpq_pq_index {
-  int d = 0, M = 0, nbits = 8, ksub = 256, metric = IVFPQ_METRIC_L2, device = 0;
-  bool trained = false;
-  std::vector<float> codebook;  // [M][256][d / M]
-  int64_t ntotal = 0, cap = 0;  // codes in the image, rows allocated
-  DevBuf d_cb, d_codes;
-  DevBuf w_x, w_tab, w_pD, w_pI, w_D, w_I;  // staging, tables, partial lists
+struct CodeStore {
+  const char* const name;  // the Faiss index, for messages
+  int device = 0;
+  int64_t ntotal = 0, cap = 0;      // codes in the image, rows allocated
+  size_t row_bytes = 0, slack = 0;  // bytes per image row, bytes allocated behind the last row
+  DevBuf d_codes;
+  DevBuf w_x;  // staging of host rows
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;  // recorded after every device call, on done_stream
   hipStream_t done_stream = nullptr;
   bool done_pending = false;
   std::mutex mu;
 
-  ~ivfpq_pq_index() {
+  explicit CodeStore(const char* index_name) : name(index_name) {}
+  ~CodeStore() {
     if (done) (void)hipEventDestroy(done);
     if (stream) (void)hipStreamDestroy(stream);
   }
-  bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
 
   void order_after(hipStream_t s) {
     if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
@@ -1828,24 +1818,19 @@ struct ivfpq_pq_index {
     done_pending = false;
   }
 
-  void upload_codebook() {
-    quiesce();
-    d_cb.ensure(sizeof(float) * codebook.size());
-    HIPCHECK(hipMemcpyAsync(d_cb.p, codebook.data(), sizeof(float) * codebook.size(), hipMemcpyHostToDevice, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    trained = true;
-  }
+  uint8_t* row(int64_t i) const { return d_codes.as<uint8_t>() + (size_t)i * row_bytes; }
 
   // room for n more codes: the image doubles (at least) when it is full
   void reserve(int64_t n, hipStream_t s) {
-    require(ntotal + n < (int64_t)INT32_MAX, "IndexPQ holds at most 2^31 - 2 codes");
+    require(ntotal + n < (int64_t)INT32_MAX, std::string(name) + " holds at most 2^31 - 2 codes");
     if (ntotal + n <= cap) return;
     quiesce();
     const int64_t ncap = std::max<int64_t>({ntotal + n, 2 * cap, 1024});
+    const size_t nbytes = (size_t)ncap * row_bytes + slack;
     void* np = nullptr;
-    HIPCHECK(hipMalloc(&np, (size_t)ncap * M));
+    HIPCHECK(hipMalloc(&np, nbytes));
     if (ntotal) {
-      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * M, hipMemcpyDeviceToDevice, s);
+      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * row_bytes, hipMemcpyDeviceToDevice, s);
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) {
         (void)hipFree(np);
@@ -1854,29 +1839,133 @@ struct ivfpq_pq_index {
     }
     d_codes.release();
     d_codes.p = np;
-    d_codes.bytes = (size_t)ncap * M;
+    d_codes.bytes = nbytes;
     cap = ncap;
+  }
+
+  // n host rows [n][row_bytes] behind the image; returns when they are in place
+  void append_rows(int64_t n, const uint8_t* codes) {
+    reserve(n, stream);
+    quiesce();
+    HIPCHECK(hipMemcpyAsync(row(ntotal), codes, (size_t)n * row_bytes, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    ntotal += n;
+  }
+
+  // the first out_bytes (<= row_bytes) of the rows [i0, i0 + n) to the host
+  void read_rows(int64_t i0, int64_t n, uint8_t* out, size_t out_bytes) {
+    quiesce();
+    if (out_bytes == row_bytes)
+      HIPCHECK(hipMemcpyAsync(out, row(i0), (size_t)n * row_bytes, hipMemcpyDeviceToHost, stream));
+    else
+      HIPCHECK(hipMemcpy2DAsync(out, out_bytes, row(i0), row_bytes, out_bytes, n, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+
+  void reset() {
+    quiesce();
+    d_codes.release();
+    ntotal = cap = 0;
+  }
+
+  // rows per chunk of n host rows of in_bytes each that pass through a staging buffer
+  static int64_t host_rows(int64_t n, size_t in_bytes) {
+    return std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / in_bytes));
+  }
+
+  // n host rows of in_bytes each, staged chunk by chunk in w_x; add(c) puts the c staged
+  // rows behind the image on the handle's stream and returns when they are in place
+  template <class F>
+  void add_host(int64_t n, const void* x, size_t in_bytes, F add) {
+    const int64_t rows = host_rows(n, in_bytes);
+    quiesce();
+    w_x.ensure((size_t)rows * in_bytes);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t c = std::min(rows, n - r0);
+      HIPCHECK(hipMemcpyAsync(w_x.p, (const uint8_t*)x + (size_t)r0 * in_bytes, (size_t)c * in_bytes,
+                              hipMemcpyHostToDevice, stream));
+      add(c);
+    }
+  }
+};
+
+// the end of every *_create: the device checked, the handle's stream and event made on it
+template <class H>
+void open_store(std::unique_ptr<H> h, int device, H** out) {
+  int ndev = 0;
+  HIPCHECK(hipGetDeviceCount(&ndev));
+  require(device >= 0 && device < ndev, "device ordinal out of range");
+  DeviceGuard g(device);
+  h->device = device;
+  HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+}
+
+// every *_free
+template <class H>
+int free_store(H* h) {
+  return guarded([&] {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->quiesce();
+    delete h;
+  });
+}
+
+// the search arguments of the three indexes (one that needs no training passes true)
+void check_search_args(bool trained, int64_t n, const void* x, int k, const void* D, const void* I) {
+  require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+  require(trained, "index is not trained");
+  require(n >= 0, "negative query count");
+  require(n == 0 || (x && D && I), "null x / D / I");
+}
+
+}  // namespace
+
+// ================================================================ flat PQ (IndexPQ)
+// faiss.IndexPQ: no coarse quantizer and no inverted lists -- one product quantizer
+// over the raw vectors, every code scanned for every query (pq_flat.hip).  The codes
+// live in a CodeStore of M bytes per row.
+namespace {
+
+// queries per chunk of a flat-PQ search: the tables (M KiB per query) within kChunkBytes,
+// the grid's y extent (shared by the handle and ivfpq_pq_debug_plan)
+int64_t pq_query_chunk(int M, int64_t n) {
+  return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
+}
+
+const char* pq_supported_M_text() { return " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)"; }
+
+}  // namespace
+
+struct ivfpq_pq_index : CodeStore {
+  int d = 0, M = 0, nbits = 8, ksub = 256, metric = IVFPQ_METRIC_L2;
+  bool trained = false;
+  std::vector<float> codebook;  // [M][256][d / M]
+  DevBuf d_cb;
+  DevBuf w_tab, w_pD, w_pI, w_D, w_I;  // tables, partial lists, results of the host entry points
+
+  ivfpq_pq_index() : CodeStore("IndexPQ") {}
+  bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
+
+  void upload_codebook() {
+    quiesce();
+    d_cb.ensure(sizeof(float) * codebook.size());
+    HIPCHECK(hipMemcpyAsync(d_cb.p, codebook.data(), sizeof(float) * codebook.size(), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    trained = true;
   }
 
   // encode n device-resident vectors behind the image; returns when they are in place
   void add_dev(int64_t n, const float* xd, hipStream_t s) {
     reserve(n, s);
     order_after(s);
-    launch_pq_encode_flat(xd, n, d, d_cb.as<float>(), M, d_codes.as<uint8_t>() + ntotal * M, s);
+    launch_pq_encode_flat(xd, n, d, d_cb.as<float>(), M, row(ntotal), s);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     ntotal += n;
-  }
-
-  void add_host(int64_t n, const float* x) {
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / (sizeof(float) * d)));
-    quiesce();
-    w_x.ensure(sizeof(float) * rows * d);
-    for (int64_t r0 = 0; r0 < n; r0 += rows) {
-      const int64_t c = std::min(rows, n - r0);
-      HIPCHECK(hipMemcpyAsync(w_x.p, x + r0 * d, sizeof(float) * c * d, hipMemcpyHostToDevice, stream));
-      add_dev(c, w_x.as<float>(), stream);
-    }
   }
 
   int64_t query_chunk(int64_t n) const { return pq_query_chunk(M, n); }
@@ -1884,7 +1973,7 @@ struct ivfpq_pq_index {
   // c device-resident queries -> D, I (device), all on s
   void search_chunk(const float* xd, int64_t c, int k, float* D, int64_t* I, hipStream_t s) {
     if (ntotal == 0) {
-      launch_pq_fill_empty(D, I, c * k, ip(), s);
+      launch_fill_empty(D, I, c * k, ip(), s);
       return;
     }
     w_tab.ensure(sizeof(float) * c * M * 256);
@@ -1932,13 +2021,6 @@ namespace {
 
 void check_pq(const ivfpq_pq_index* h) { require(h != nullptr, "null index handle"); }
 
-void check_search_args(const ivfpq_pq_index* h, int64_t n, const void* x, int k, const void* D, const void* I) {
-  require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
-  require(h->trained, "index is not trained");
-  require(n >= 0, "negative query count");
-  require(n == 0 || (x && D && I), "null x / D / I");
-}
-
 }  // namespace
 
 extern "C" {
@@ -1952,31 +2034,17 @@ int ivfpq_pq_create(int d, int M, int nbits, int metric, int device, ivfpq_pq_in
     require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
     require(d <= 2048, "d > 2048 not supported");
     require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
-    int ndev = 0;
-    HIPCHECK(hipGetDeviceCount(&ndev));
-    require(device >= 0 && device < ndev, "device ordinal out of range");
-    DeviceGuard g(device);
     auto h = std::make_unique<ivfpq_pq_index>();
     h->d = d;
     h->M = M;
     h->nbits = nbits;
     h->metric = metric;
-    h->device = device;
-    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-    *out = h.release();
+    h->row_bytes = (size_t)M;
+    open_store(std::move(h), device, out);
   });
 }
 
-int ivfpq_pq_free(ivfpq_pq_index* h) {
-  return guarded([&] {
-    if (!h) return;
-    DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    h->quiesce();
-    delete h;
-  });
-}
+int ivfpq_pq_free(ivfpq_pq_index* h) { return free_store(h); }
 
 int ivfpq_pq_train(ivfpq_pq_index* h, int64_t n, const float* x, int niter, uint64_t seed) {
   return guarded([&] {
@@ -2021,7 +2089,7 @@ int ivfpq_pq_add(ivfpq_pq_index* h, int64_t n, const float* x) {
     require(h->trained, "index is not trained");
     if (n <= 0) return;
     require(x != nullptr, "null x");
-    h->add_host(n, x);
+    h->add_host(n, x, sizeof(float) * h->d, [&](int64_t c) { h->add_dev(c, h->w_x.as<float>(), h->stream); });
   });
 }
 
@@ -2045,12 +2113,7 @@ int ivfpq_pq_add_codes(ivfpq_pq_index* h, int64_t n, const uint8_t* codes) {
     require(h->trained, "index is not trained");
     if (n <= 0) return;
     require(codes != nullptr, "null codes");
-    h->reserve(n, h->stream);
-    h->quiesce();
-    HIPCHECK(hipMemcpyAsync(h->d_codes.as<uint8_t>() + h->ntotal * h->M, codes, (size_t)n * h->M,
-                            hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    h->ntotal += n;
+    h->append_rows(n, codes);
   });
 }
 
@@ -2059,16 +2122,14 @@ int ivfpq_pq_reset(ivfpq_pq_index* h) {
     check_pq(h);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->quiesce();
-    h->d_codes.release();
-    h->ntotal = h->cap = 0;
+    h->reset();
   });
 }
 
 int ivfpq_pq_search(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I) {
   return guarded([&] {
     check_pq(h);
-    check_search_args(h, n, x, k, D, I);
+    check_search_args(h->trained, n, x, k, D, I);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     if (n == 0) return;
@@ -2079,7 +2140,7 @@ int ivfpq_pq_search(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* 
 int ivfpq_pq_search_device(ivfpq_pq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I, void* stream) {
   return guarded([&] {
     check_pq(h);
-    check_search_args(h, n, x, k, D, I);
+    check_search_args(h->trained, n, x, k, D, I);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     if (n == 0) return;
@@ -2118,10 +2179,7 @@ int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out) {
     require(i0 >= 0 && n >= 0 && i0 + n <= h->ntotal, "code range outside [0, ntotal)");
     if (n == 0) return;
     require(out != nullptr, "null output pointer");
-    h->quiesce();
-    HIPCHECK(hipMemcpyAsync(out, h->d_codes.as<uint8_t>() + i0 * h->M, (size_t)n * h->M, hipMemcpyDeviceToHost,
-                            h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->read_rows(i0, n, out, h->row_bytes);
   });
 }
 
@@ -2385,7 +2443,7 @@ struct ivfpq_ivfflat_index {
     if (n == 0) return;
     order_after(s);
     if (img_n == 0) {
-      launch_ivfflat_fill_empty(D, I, n * k, ip(), s);
+      launch_fill_empty(D, I, n * k, ip(), s);
       HIPCHECK(hipGetLastError());
       mark_done(s);
       return;
@@ -2688,10 +2746,8 @@ int ivfpq_ivfflat_get_list(ivfpq_ivfflat_index* h, int list, float* vectors, int
 // ============================================================ flat scalar quantizer (IndexScalarQuantizer)
 // faiss.IndexScalarQuantizer: every component stored as a half or as an 8-bit code
 // between the trained per-dimension (or global) minimum and maximum, every code scanned
-// for every query with the decode fused in (sq_scan.hip).  The codes live in one device
-// image [ntotal][code_size] that grows geometrically (with the scan's read slack behind
-// it); the label of a code is its position.  Device calls on different streams are
-// ordered one after the other (one workspace per handle).
+// for every query with the decode fused in (sq_scan.hip).  The codes live in a CodeStore
+// of code_size bytes per row, with the scan's read slack behind the image.
 namespace {
 
 const char* sq_qtype_name(int qtype) {
@@ -2709,40 +2765,19 @@ const char* sq_qtype_name(int qtype) {
 
 }  // namespace
 
-struct ivfpq_sq_index {
-  int d = 0, qtype = IVFPQ_SQ_FP16, metric = IVFPQ_METRIC_L2, device = 0;
+struct ivfpq_sq_index : CodeStore {
+  int d = 0, qtype = IVFPQ_SQ_FP16, metric = IVFPQ_METRIC_L2;
   int codec = SQ_CODEC_FP16, code_size = 0;
   bool trained = false;
-  std::vector<float> params;    // Faiss's sq.trained: [vmin (d), vdiff (d)], [vmin, vdiff] (uniform) or empty (fp16)
-  int64_t ntotal = 0, cap = 0;  // codes in the image, rows allocated
-  DevBuf d_vmin, d_vdiff, d_codes;
-  DevBuf w_x, w_codes, w_mm, w_D, w_I, p_tau, p_partD, p_partI, p_tmpD, p_tmpI;
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // recorded after every device call, on done_stream
-  hipStream_t done_stream = nullptr;
-  bool done_pending = false;
-  std::mutex mu;
+  std::vector<float> params;  // Faiss's sq.trained: [vmin (d), vdiff (d)], [vmin, vdiff] (uniform) or empty (fp16)
+  DevBuf d_vmin, d_vdiff;
+  DevBuf w_codes, w_mm, w_D, w_I, p_tau, p_partD, p_partI, p_tmpD, p_tmpI;
 
-  ~ivfpq_sq_index() {
-    if (done) (void)hipEventDestroy(done);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  ivfpq_sq_index() : CodeStore("IndexScalarQuantizer") {}
   bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
   bool uniform() const { return qtype == IVFPQ_SQ_8BIT_UNIFORM; }
   size_t nparams() const { return codec == SQ_CODEC_FP16 ? 0 : uniform() ? 2 : 2 * (size_t)d; }
-
-  void order_after(hipStream_t s) {
-    if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
-  }
-  void mark_done(hipStream_t s) {
-    HIPCHECK(hipEventRecord(done, s));
-    done_stream = s;
-    done_pending = true;
-  }
-  void quiesce() {
-    if (done_pending) HIPCHECK(hipEventSynchronize(done));
-    done_pending = false;
-  }
+  int64_t host_rows(int64_t n) const { return CodeStore::host_rows(n, sizeof(float) * d); }
 
   // the 8-bit codec's device parameters: per dimension, a uniform pair repeated d times
   void upload_params() {
@@ -2766,7 +2801,7 @@ struct ivfpq_sq_index {
   void train_host(int64_t n, const float* x) {
     if (codec == SQ_CODEC_FP16) return;
     quiesce();
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / (sizeof(float) * d)));
+    const int64_t rows = host_rows(n);
     w_x.ensure(sizeof(float) * rows * d);
     w_mm.ensure(sizeof(uint32_t) * 2 * d);
     uint32_t* lo = w_mm.as<uint32_t>();
@@ -2801,53 +2836,14 @@ struct ivfpq_sq_index {
     upload_params();
   }
 
-  // room for n more codes: the image doubles (at least) when it is full
-  void reserve(int64_t n, hipStream_t s) {
-    require(ntotal + n < (int64_t)INT32_MAX, "IndexScalarQuantizer holds at most 2^31 - 2 codes");
-    if (ntotal + n <= cap) return;
-    quiesce();
-    const int64_t ncap = std::max<int64_t>({ntotal + n, 2 * cap, 1024});
-    const size_t nbytes = (size_t)ncap * code_size + kSqScanSlack;
-    void* np = nullptr;
-    HIPCHECK(hipMalloc(&np, nbytes));
-    if (ntotal) {
-      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * code_size, hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) {
-        (void)hipFree(np);
-        HIPCHECK(e);
-      }
-    }
-    d_codes.release();
-    d_codes.p = np;
-    d_codes.bytes = nbytes;
-    cap = ncap;
-  }
-
   // encode n device-resident vectors behind the image; returns when they are in place
   void add_dev(int64_t n, const float* xd, hipStream_t s) {
     reserve(n, s);
     order_after(s);
-    launch_sq_encode(codec, xd, n, d, d_vmin.as<float>(), d_vdiff.as<float>(),
-                     d_codes.as<uint8_t>() + ntotal * code_size, s);
+    launch_sq_encode(codec, xd, n, d, d_vmin.as<float>(), d_vdiff.as<float>(), row(ntotal), s);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     ntotal += n;
-  }
-
-  int64_t host_rows(int64_t n) const {
-    return std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / (sizeof(float) * d)));
-  }
-
-  void add_host(int64_t n, const float* x) {
-    const int64_t rows = host_rows(n);
-    quiesce();
-    w_x.ensure(sizeof(float) * rows * d);
-    for (int64_t r0 = 0; r0 < n; r0 += rows) {
-      const int64_t c = std::min(rows, n - r0);
-      HIPCHECK(hipMemcpyAsync(w_x.p, x + r0 * d, sizeof(float) * c * d, hipMemcpyHostToDevice, stream));
-      add_dev(c, w_x.as<float>(), stream);
-    }
   }
 
   // sa_encode / sa_decode of host buffers, in chunks through the staging buffers
@@ -2882,19 +2878,12 @@ struct ivfpq_sq_index {
     }
   }
 
-  void check_search(int64_t n, const void* x, int k, const void* D, const void* I) const {
-    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
-    require(trained, "index is not trained");
-    require(n >= 0, "negative query count");
-    require(n == 0 || (x && D && I), "null x / D / I");
-  }
-
   // n device-resident queries -> D, I (device), all on s
   void search_dev(int64_t n, const float* xd, int k, float* D, int64_t* I, hipStream_t s) {
     if (n == 0) return;
     order_after(s);
     if (ntotal == 0) {
-      launch_ivfflat_fill_empty(D, I, n * k, ip(), s);
+      launch_fill_empty(D, I, n * k, ip(), s);
       HIPCHECK(hipGetLastError());
       mark_done(s);
       return;
@@ -2966,33 +2955,20 @@ int ivfpq_sq_create(int d, int qtype, int metric, int device, ivfpq_sq_index** o
     require(qtype == IVFPQ_SQ_8BIT || qtype == IVFPQ_SQ_8BIT_UNIFORM || qtype == IVFPQ_SQ_FP16,
             std::string("scalar quantizer type ") + qn + " is not supported (QT_fp16, QT_8bit, QT_8bit_uniform)");
     require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
-    int ndev = 0;
-    HIPCHECK(hipGetDeviceCount(&ndev));
-    require(device >= 0 && device < ndev, "device ordinal out of range");
-    DeviceGuard g(device);
     auto h = std::make_unique<ivfpq_sq_index>();
     h->d = d;
     h->qtype = qtype;
     h->codec = qtype == IVFPQ_SQ_FP16 ? SQ_CODEC_FP16 : SQ_CODEC_8BIT;
     h->code_size = sq_code_size(h->codec, d);
+    h->row_bytes = (size_t)h->code_size;
+    h->slack = kSqScanSlack;  // the scan's 16-byte loads may straddle the last row's end
     h->metric = metric;
-    h->device = device;
     h->trained = qtype == IVFPQ_SQ_FP16;  // nothing to train
-    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-    *out = h.release();
+    open_store(std::move(h), device, out);
   });
 }
 
-int ivfpq_sq_free(ivfpq_sq_index* h) {
-  return guarded([&] {
-    if (!h) return;
-    DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    h->quiesce();
-    delete h;
-  });
-}
+int ivfpq_sq_free(ivfpq_sq_index* h) { return free_store(h); }
 
 int ivfpq_sq_train(ivfpq_sq_index* h, int64_t n, const float* x) {
   return guarded([&] {
@@ -3025,7 +3001,7 @@ int ivfpq_sq_add(ivfpq_sq_index* h, int64_t n, const float* x) {
     require(x != nullptr, "null x");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->add_host(n, x);
+    h->add_host(n, x, sizeof(float) * h->d, [&](int64_t c) { h->add_dev(c, h->w_x.as<float>(), h->stream); });
   });
 }
 
@@ -3049,12 +3025,7 @@ int ivfpq_sq_add_codes(ivfpq_sq_index* h, int64_t n, const uint8_t* codes) {
     require(codes != nullptr, "null codes");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->reserve(n, h->stream);
-    h->quiesce();
-    HIPCHECK(hipMemcpyAsync(h->d_codes.as<uint8_t>() + h->ntotal * h->code_size, codes, (size_t)n * h->code_size,
-                            hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    h->ntotal += n;
+    h->append_rows(n, codes);
   });
 }
 
@@ -3063,16 +3034,14 @@ int ivfpq_sq_reset(ivfpq_sq_index* h) {
     check_sq(h);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->quiesce();
-    h->d_codes.release();
-    h->ntotal = h->cap = 0;
+    h->reset();
   });
 }
 
 int ivfpq_sq_search(ivfpq_sq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I) {
   return guarded([&] {
     check_sq(h);
-    h->check_search(n, x, k, D, I);
+    check_search_args(h->trained, n, x, k, D, I);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     h->search_host(n, x, k, D, I);
@@ -3082,7 +3051,7 @@ int ivfpq_sq_search(ivfpq_sq_index* h, int64_t n, const float* x, int k, float* 
 int ivfpq_sq_search_device(ivfpq_sq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I, void* stream) {
   return guarded([&] {
     check_sq(h);
-    h->check_search(n, x, k, D, I);
+    check_search_args(h->trained, n, x, k, D, I);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     h->search_dev(n, x, k, D, I, (hipStream_t)stream);
@@ -3120,10 +3089,7 @@ int ivfpq_sq_get_codes(ivfpq_sq_index* h, int64_t i0, int64_t n, uint8_t* out) {
     if (n == 0) return;
     require(out != nullptr, "null output pointer");
     DeviceGuard g(h->device);
-    h->quiesce();
-    HIPCHECK(hipMemcpyAsync(out, h->d_codes.as<uint8_t>() + i0 * h->code_size, (size_t)n * h->code_size,
-                            hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->read_rows(i0, n, out, h->row_bytes);
   });
 }
 
@@ -3156,60 +3122,13 @@ int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x
 // ============================================================ flat binary codes (IndexBinaryFlat)
 // faiss.IndexBinaryFlat: uint8 codes of d bits, every code compared with every query by
 // Hamming distance and the k smallest (distance, label) selected by counting
-// (binary_flat.hip).  The codes live in one device image [ntotal][stride] (rows padded with
-// zero bytes to whole loads) that grows geometrically; the label of a code is its position.
-// Device calls on different streams are ordered one after the other (one workspace per handle).
-struct ivfpq_bin_index {
-  int d = 0, code_size = 0, stride = 0, device = 0;
-  int64_t ntotal = 0, cap = 0;  // codes in the image, rows allocated
-  DevBuf d_codes;
-  DevBuf w_x, w_D, w_I, p_qw, p_hist, p_T, p_quota;
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // recorded after every device call, on done_stream
-  hipStream_t done_stream = nullptr;
-  bool done_pending = false;
-  std::mutex mu;
+// (binary_flat.hip).  The codes live in a CodeStore of stride bytes per row (rows padded
+// with zero bytes to whole loads).
+struct ivfpq_bin_index : CodeStore {
+  int d = 0, code_size = 0, stride = 0;  // stride = row_bytes: a row padded to whole loads
+  DevBuf w_D, w_I, p_qw, p_hist, p_T, p_quota;
 
-  ~ivfpq_bin_index() {
-    if (done) (void)hipEventDestroy(done);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-
-  void order_after(hipStream_t s) {
-    if (done_pending && done_stream != s) HIPCHECK(hipStreamWaitEvent(s, done, 0));
-  }
-  void mark_done(hipStream_t s) {
-    HIPCHECK(hipEventRecord(done, s));
-    done_stream = s;
-    done_pending = true;
-  }
-  void quiesce() {
-    if (done_pending) HIPCHECK(hipEventSynchronize(done));
-    done_pending = false;
-  }
-
-  // room for n more codes: the image doubles (at least) when it is full
-  void reserve(int64_t n, hipStream_t s) {
-    require(ntotal + n < (int64_t)INT32_MAX, "IndexBinaryFlat holds at most 2^31 - 2 codes");
-    if (ntotal + n <= cap) return;
-    quiesce();
-    const int64_t ncap = std::max<int64_t>({ntotal + n, 2 * cap, 1024});
-    const size_t nbytes = (size_t)ncap * stride;
-    void* np = nullptr;
-    HIPCHECK(hipMalloc(&np, nbytes));
-    if (ntotal) {
-      hipError_t e = hipMemcpyAsync(np, d_codes.p, (size_t)ntotal * stride, hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) {
-        (void)hipFree(np);
-        HIPCHECK(e);
-      }
-    }
-    d_codes.release();
-    d_codes.p = np;
-    d_codes.bytes = nbytes;
-    cap = ncap;
-  }
+  ivfpq_bin_index() : CodeStore("IndexBinaryFlat") {}
 
   // pad n device-resident codes [n][code_size] behind the image; returns when they are in place
   void add_dev(int64_t n, const uint8_t* xd, hipStream_t s) {
@@ -3219,17 +3138,6 @@ struct ivfpq_bin_index {
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     ntotal += n;
-  }
-
-  void add_host(int64_t n, const uint8_t* x) {
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / code_size));
-    quiesce();
-    w_x.ensure((size_t)rows * code_size);
-    for (int64_t r0 = 0; r0 < n; r0 += rows) {
-      const int64_t c = std::min(rows, n - r0);
-      HIPCHECK(hipMemcpyAsync(w_x.p, x + r0 * code_size, (size_t)c * code_size, hipMemcpyHostToDevice, stream));
-      add_dev(c, w_x.as<uint8_t>(), stream);
-    }
   }
 
   // n device-resident queries -> D, I (device), all on s
@@ -3289,11 +3197,6 @@ void check_bin_d(int d) {
   require(d >= 8 && d <= kBinMaxD && d % 8 == 0,
           "IndexBinaryFlat: d must be a multiple of 8 in [8, 2048] (d = " + std::to_string(d) + ")");
 }
-void check_bin_search(int64_t n, const void* x, int k, const void* D, const void* I) {
-  require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
-  require(n >= 0, "negative query count");
-  require(n == 0 || (x && D && I), "null x / D / I");
-}
 }  // namespace
 
 extern "C" {
@@ -3302,39 +3205,23 @@ int ivfpq_bin_create(int d, int device, ivfpq_bin_index** out) {
   return guarded([&] {
     require(out != nullptr, "null output pointer");
     check_bin_d(d);
-    int ndev = 0;
-    HIPCHECK(hipGetDeviceCount(&ndev));
-    require(device >= 0 && device < ndev, "device ordinal out of range");
-    DeviceGuard g(device);
     auto h = std::make_unique<ivfpq_bin_index>();
     h->d = d;
     h->code_size = d / 8;
     h->stride = bin_stride(h->code_size);
-    h->device = device;
-    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-    *out = h.release();
+    h->row_bytes = (size_t)h->stride;
+    open_store(std::move(h), device, out);
   });
 }
 
-int ivfpq_bin_free(ivfpq_bin_index* h) {
-  return guarded([&] {
-    if (!h) return;
-    DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    h->quiesce();
-    delete h;
-  });
-}
+int ivfpq_bin_free(ivfpq_bin_index* h) { return free_store(h); }
 
 int ivfpq_bin_reset(ivfpq_bin_index* h) {
   return guarded([&] {
     check_bin(h);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->quiesce();
-    h->d_codes.release();
-    h->ntotal = h->cap = 0;
+    h->reset();
   });
 }
 
@@ -3345,7 +3232,7 @@ int ivfpq_bin_add(ivfpq_bin_index* h, int64_t n, const uint8_t* x) {
     require(x != nullptr, "null x");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    h->add_host(n, x);
+    h->add_host(n, x, (size_t)h->code_size, [&](int64_t c) { h->add_dev(c, h->w_x.as<uint8_t>(), h->stream); });
   });
 }
 
@@ -3362,7 +3249,7 @@ int ivfpq_bin_add_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, void* 
 
 int ivfpq_bin_search(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I) {
   return guarded([&] {
-    check_bin_search(n, x, k, D, I);
+    check_search_args(true, n, x, k, D, I);  // nothing to train
     check_bin(h);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
@@ -3373,7 +3260,7 @@ int ivfpq_bin_search(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int
 int ivfpq_bin_search_device(ivfpq_bin_index* h, int64_t n, const uint8_t* x, int k, int32_t* D, int64_t* I,
                             void* stream) {
   return guarded([&] {
-    check_bin_search(n, x, k, D, I);
+    check_search_args(true, n, x, k, D, I);  // nothing to train
     check_bin(h);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
@@ -3399,14 +3286,7 @@ int ivfpq_bin_get_codes(ivfpq_bin_index* h, int64_t i0, int64_t n, uint8_t* out)
     if (n == 0) return;
     require(out != nullptr, "null output pointer");
     DeviceGuard g(h->device);
-    h->quiesce();
-    const uint8_t* src = h->d_codes.as<uint8_t>() + (size_t)i0 * h->stride;
-    if (h->stride == h->code_size)
-      HIPCHECK(hipMemcpyAsync(out, src, (size_t)n * h->code_size, hipMemcpyDeviceToHost, h->stream));
-    else  // the rows without their pad bytes
-      HIPCHECK(hipMemcpy2DAsync(out, h->code_size, src, h->stride, h->code_size, n, hipMemcpyDeviceToHost,
-                                h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->read_rows(i0, n, out, (size_t)h->code_size);  // the rows without their pad bytes
   });
 }
 

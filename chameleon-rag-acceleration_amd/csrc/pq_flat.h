@@ -40,7 +40,4 @@ PqScanPlan pq_scan_plan(int M, int k, int64_t nq, int64_t nb);
 void launch_pq_scan(const float* tab, int64_t nq, const uint8_t* codes, int64_t nb, int M, int k, bool ip,
                     const PqScanPlan& plan, float* partD, int64_t* partI, hipStream_t s);
 
-// D[i] = FLT_MAX (-FLT_MAX for ip), I[i] = -1: the result of searching an empty index
-void launch_pq_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s);
-
 }  // namespace chivf

@@ -1,9 +1,14 @@
-// Device code shared by the list-major exact scans (ivf_flat.hip, sq_scan.hip): the
-// wave top-k in registers over (key, int32 position) pairs, the per-query shared
-// bound, the LDS candidate queue of k > 64, and the host loop that merges the scans'
-// sorted partial lists in rounds.  Everything is in an anonymous namespace: each
+// Device code shared by the flat scans (pq_flat.hip, ivf_flat.hip, sq_scan.hip): the wave
+// top-k in registers over (key, int32 position) pairs, the per-query shared bound of the
+// exact scans, the LDS candidate queue of k > 64, the tail of a scan pass (distance
+// terms, the fold to a key, admission, drain sites, the sorted write) and the host loop
+// that merges the exact scans' sorted partial lists in rounds.  k_pq_scan and
+// k_ivfflat_scan take their pass tail from here; k_sq_scan uses the top-k, the bound and
+// the queue but spells its tail out, because it measured slower on the helpers
+// (profiles/flat_scans_refactor.md).  Everything is in an anonymous namespace: each
 // translation unit compiles its own copy, inlined into its kernels.
 #pragma once
+#include <float.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -20,6 +25,11 @@ constexpr float kInf = __builtin_huge_valf();
 constexpr int kNone = INT32_MAX;  // "no candidate" position (real positions are < 2^31 - 1)
 
 enum { K_IP = 0, K_L2 = 1 };
+
+inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+// rows of 64 lanes in a wave's top-k: the three k classes of every flat scan
+inline int scan_rows_for(int k) { return k <= 64 ? 1 : k <= 256 ? 4 : 16; }
 
 // ---- wave top-k in registers (int32 positions) ---------------------------------
 __device__ __forceinline__ bool lexless(float ad, int ai, float bd, int bi) {
@@ -61,6 +71,7 @@ struct WaveTopK {
   float td;  // the admission threshold: the current k-th best, or the query's shared bound where that is lower
   int ti;
   int krow, klane;
+  // the shared bound (a scan that never calls set_cap / publish keeps both at +inf, and they fold away)
   float cap;  // the query's shared bound as last read (every key above it is outside the final top-k)
   float pub;  // the k-th best this wave last published to the shared bound
 
@@ -178,29 +189,150 @@ __device__ __forceinline__ void WaveTopK<R>::publish(uint32_t* tau_q, int lane) 
   }
 }
 
-constexpr int kQueue = 64 + 64;  // queued candidates per (wave, query): < 64 pending + a pass's pushes
+// Queued candidates per (wave, query) when a pass pushes at most NB per lane: < 64
+// pending + a pass's pushes.  NB = 1 for the exact scans (one row per lane and pass).
+template <int NB>
+constexpr int kQueue = 64 + NB * 64;
 
 // The first min(n, 64) candidates of a wave's queue (q_d, q_i) into its top-k, the
-// rest moved to the front; n becomes the number left.
-template <int R>
+// rest (up to NB blocks of 64) moved to the front; n becomes the number left.
+template <int R, int NB>
 __device__ __forceinline__ void drain_queue(WaveTopK<R>& tk, int& n, float* q_d, int* q_i, int lane) {
   __builtin_amdgcn_wave_barrier();
   const bool have = lane < n;
   const float cd = have ? q_d[lane] : kInf;
   const int ci = have ? q_i[lane] : kNone;
   const int rem = max(n - 64, 0);
-  const bool mv = lane < rem;
-  const float md = mv ? q_d[64 + lane] : kInf;
-  const int mi = mv ? q_i[64 + lane] : kNone;
+  float md[NB];
+  int mi[NB];
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    const bool mv = j * 64 + lane < rem;
+    md[j] = mv ? q_d[64 + j * 64 + lane] : kInf;
+    mi[j] = mv ? q_i[64 + j * 64 + lane] : kNone;
+  }
   __builtin_amdgcn_wave_barrier();
-  if (mv) {
-    q_d[lane] = md;
-    q_i[lane] = mi;
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    if (j * 64 + lane < rem) {
+      q_d[j * 64 + lane] = md[j];
+      q_i[j * 64 + lane] = mi[j];
+    }
   }
   __builtin_amdgcn_wave_barrier();
   n = rem;
   const bool pass = lexless(cd, ci, tk.td, tk.ti);  // the bound may have moved since the push
   if (__ballot(pass)) bulk_merge_rows<R>(tk, pass ? cd : kInf, pass ? ci : kNone, lane);
+}
+
+// ---- the tail of a scan pass -----------------------------------------------------
+// One term of a distance: (q - y)^2, or q * y for the inner product.
+template <int KIND>
+__device__ __forceinline__ float dist_term(float q, float y) {
+  if (KIND == K_IP) return q * y;
+  const float t = q - y;
+  return t * t;
+}
+
+// Eight values of the lane's row at dimensions [dim0, dim0 + 8) against the G query rows
+// qid of x (wave-uniform: they come through the scalar cache), into Faiss's eight
+// interleaved accumulators per query.
+template <int KIND, int G>
+__device__ __forceinline__ void accumulate8(float (&acc)[G][8], const float (&y)[8], const float* x, int d,
+                                            const int (&qid)[G], int dim0) {
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    const float* qp = x + (int64_t)qid[g] * d + dim0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[g][j] = acc[g][j] + dist_term<KIND>(qp[j], y[j]);
+  }
+}
+
+// The end of a row in tree<>'s order: the eight accumulators folded to four, the 4-wide
+// remainder y against qp (when rem), two horizontal adds.  Returns the key (the negated
+// similarity for the inner product) and zeroes the accumulators for the next row.
+template <int KIND>
+__device__ __forceinline__ float fold_key(float (&acc)[8], bool rem, const float* qp, const float (&y)[4]) {
+  float a4[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) a4[j] = acc[j + 4] + acc[j];
+  if (rem) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) a4[j] = a4[j] + dist_term<KIND>(qp[j], y[j]);
+  }
+  const float h0 = a4[0] + a4[1];
+  const float h1 = a4[2] + a4[3];
+  const float dis = h0 + h1;
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = 0.f;
+  return KIND == K_IP ? -dis : dis;
+}
+
+// Admission of one (key, position) per lane against a query's running k-th best; a pass
+// with no better row costs one compare and one ballot.  R = 1 merges the admitted rows at
+// once and returns true (the top-k changed: an exact scan then publishes its k-th key);
+// R > 1 pushes them behind the n candidates of the (wave, query) queue (q_d, q_i).
+template <int R>
+__device__ __forceinline__ bool admit(WaveTopK<R>& tk, bool valid, float key, int pos, int& n, float* q_d, int* q_i,
+                                      int lane) {
+  const bool pass = valid & lexless(key, pos, tk.td, tk.ti);
+  const uint64_t mask = __ballot(pass);
+  if (!mask) return false;
+  if constexpr (R == 1) {
+    bulk_merge_rows<R>(tk, pass ? key : kInf, pass ? pos : kNone, lane);
+    return true;
+  } else {
+    const int before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+    if (pass) {
+      q_d[n + before] = key;
+      q_i[n + before] = pos;
+    }
+    n += __popcll(mask);
+    return false;
+  }
+}
+
+// The drain sites of a pass, one per query: the queues (qd, qi: [waves][G][kQueue<NB>])
+// drained down to `keep` candidates -- full batches of 64 after every pass (keep = 63), the
+// rest after the last (keep = 0).  PUB: an exact scan then publishes the k-th key of query
+// qid[g] to its shared bound in tau; a scan without one passes nullptr for both.
+// (Spelled out per query: a loop over g around R = 16 merges is past the compiler's
+// unroll budget, and the top-k arrays would then live in scratch.  A flag and not a
+// functor: a capturing lambda here costs the exact scans their second wave per SIMD.)
+template <int NB, bool PUB, int G, int R>
+__device__ __forceinline__ void drain_queues(WaveTopK<R> (&tk)[G], int (&qn)[G], int keep, float* qd, int* qi, int wave,
+                                             int lane, uint32_t* tau, const int* qid) {
+  static_assert(G <= 4, "drain sites are spelled out for up to four queries");
+#define SCAN_DRAIN(g)                                                                                             \
+  if constexpr (G > g) {                                                                                          \
+    while (qn[g] > keep)                                                                                          \
+      drain_queue<R, NB>(tk[g], qn[g], qd + (wave * G + g) * kQueue<NB>, qi + (wave * G + g) * kQueue<NB>, lane); \
+    if constexpr (PUB) tk[g].publish(tau + qid[g], lane);                                                         \
+  }
+  SCAN_DRAIN(0);
+  SCAN_DRAIN(1);
+  SCAN_DRAIN(2);
+  SCAN_DRAIN(3);
+#undef SCAN_DRAIN
+}
+
+// A wave's sorted list to D, I[0, k): distances or similarities (keys negated back for the
+// inner product), best first, padded with (FLT_MAX | -FLT_MAX, -1); label(pos) is the
+// int64 label of image position pos.
+template <int R, class Label>
+__device__ __forceinline__ void write_sorted(const WaveTopK<R>& tk, int k, bool ip, float* D, int64_t* I, int lane,
+                                             Label label) {
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int idx = r * 64 + lane;
+    if (idx < k) {
+      const int pos = tk.id[r];
+      const bool none = pos == kNone;
+      const float key = tk.d[r];
+      D[idx] = none ? (ip ? -FLT_MAX : FLT_MAX) : (ip ? -key : key);
+      I[idx] = none ? -1 : label(pos);
+    }
+  }
 }
 
 // Merge rounds over a scan's partial lists.  A round over S lists [S][nq][k] with fan f

@@ -23,7 +23,10 @@
 //    item = range * groups + group (range-major, so that the groups of a row range run
 //    at about the same time and find its codes in the L2).
 //    Shared bound, register top-k, LDS queues for k > 64 and the merge rounds are those
-//    of the IVF-Flat scan (scan_topk.h).
+//    of the IVF-Flat scan (scan_topk.h).  The tail of a pass (terms, fold, admission,
+//    drain sites, sorted write) is spelled out here and not taken from scan_topk.h's
+//    helpers as in k_ivfflat_scan: with them this kernel measured slower (4.8 % at
+//    d = 768, fp16, k = 10; profiles/flat_scans_refactor.md).
 // Compiled with -ffp-contract=off like the rest of the library.
 #include <float.h>
 #include <stdint.h>
@@ -44,8 +47,6 @@ using u4 = uint32_t __attribute__((ext_vector_type(4)));  // 16 bytes of codes, 
 typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
 using h8 = _Float16 __attribute__((ext_vector_type(8)));
 using h4 = _Float16 __attribute__((ext_vector_type(4)));
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ------------------------------------------------------------- encode / decode
 template <int CODEC>
@@ -119,6 +120,7 @@ __global__ __launch_bounds__(256) void k_sq_minmax(const float* __restrict__ x, 
 constexpr int kDc = SQ_SCAN_STEP_DIMS;  // dimensions per staged step (a multiple of 16)
 static_assert(kDc % 16 == 0 && kDc >= 16 && kDc <= 128, "a step is whole 16-byte pieces of either codec");
 constexpr int kTile = 256;  // rows per pass: one per thread
+constexpr int kQ = kQueue<1>;  // queued candidates per (wave, query): one push per lane and pass
 
 template <int CODEC>
 struct Layout {
@@ -142,8 +144,8 @@ __global__ __launch_bounds__(256) void k_sq_scan(const float* __restrict__ x, in
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTile * L::kStride];
   __shared__ float unit[k8bit ? 256 : 1];  // (code + 0.5f) / 255.0f
   constexpr bool kQueued = R > 1;
-  __shared__ float qd[kQueued ? kIvfFlatWaves * G * kQueue : 1];
-  __shared__ int qi[kQueued ? kIvfFlatWaves * G * kQueue : 1];
+  __shared__ float qd[kQueued ? kIvfFlatWaves * G * kQ : 1];
+  __shared__ int qi[kQueued ? kIvfFlatWaves * G * kQ : 1];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(256) void k_sq_scan(const float* __restrict__ x, in
             const int before =
                 __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
             if (pass) {
-              const int at = (wave * G + g) * kQueue + qn[g] + before;
+              const int at = (wave * G + g) * kQ + qn[g] + before;
               qd[at] = key;
               qi[at] = (int)rowpos;
             }
@@ -333,7 +335,7 @@ __global__ __launch_bounds__(256) void k_sq_scan(const float* __restrict__ x, in
 #define SQ_DRAIN(g)                                                                                   \
   if constexpr (G > g) {                                                                              \
     while (qn[g] > keep)                                                                              \
-      drain_queue<R>(tk[g], qn[g], qd + (wave * G + g) * kQueue, qi + (wave * G + g) * kQueue, lane); \
+      drain_queue<R, 1>(tk[g], qn[g], qd + (wave * G + g) * kQ, qi + (wave * G + g) * kQ, lane); \
     tk[g].publish(tau + qid[g], lane);                                                                \
   }
           SQ_DRAIN(0);
@@ -431,7 +433,7 @@ void launch_sq_search(const SqScanArgs& a, const IvfFlatPlan& p, hipStream_t s) 
   const int64_t written = sq_scan_ranges(a.nb) * kIvfFlatWaves;
   if (written < p.S) {
     const int64_t at = written * a.nq * a.k;
-    launch_ivfflat_fill_empty(a.partD + at, a.partI + at, (int64_t)p.S * a.nq * a.k - at, a.ip, s);
+    launch_fill_empty(a.partD + at, a.partI + at, (int64_t)p.S * a.nq * a.k - at, a.ip, s);
   }
   if (a.ip)
     launch_scan_kind<K_IP>(a, p, s);

@@ -30,10 +30,10 @@ for p in (REPO, os.path.join(REPO, "chameleon-rag-acceleration_amd")):
 KERNELS = {
     "k_pq_scan<4,1,8>": {"vgprs": 176, "agprs": 0, "lds_kib": 32, "workgroups_per_cu": 2},
     "k_pq_scan<4,1,16>": {"vgprs": 218, "agprs": 0, "lds_kib": 64, "workgroups_per_cu": 2},
-    "k_pq_scan<4,4,8>": {"vgprs": 221, "agprs": 0, "lds_kib": 72, "workgroups_per_cu": 2},
-    "k_pq_scan<4,4,16>": {"vgprs": 233, "agprs": 0, "lds_kib": 104, "workgroups_per_cu": 1},
-    "k_pq_scan<4,16,8>": {"vgprs": 256, "agprs": 13, "lds_kib": 72, "workgroups_per_cu": 1},
-    "k_pq_scan<4,16,16>": {"vgprs": 256, "agprs": 34, "lds_kib": 104, "workgroups_per_cu": 1},
+    "k_pq_scan<4,4,8>": {"vgprs": 223, "agprs": 0, "lds_kib": 72, "workgroups_per_cu": 2},
+    "k_pq_scan<4,4,16>": {"vgprs": 235, "agprs": 0, "lds_kib": 104, "workgroups_per_cu": 1},
+    "k_pq_scan<4,16,8>": {"vgprs": 256, "agprs": 15, "lds_kib": 72, "workgroups_per_cu": 1},
+    "k_pq_scan<4,16,16>": {"vgprs": 256, "agprs": 36, "lds_kib": 104, "workgroups_per_cu": 1},
 }
 LDS_PEAK_BYTES_PER_S = 256 * 256 * 2.4e9  # 256 B/clk/CU (ds_read_b128) x 256 CUs x 2.4 GHz
 

@@ -11,6 +11,7 @@ from .index import (  # noqa: F401
     METRIC_INNER_PRODUCT,
     METRIC_L2,
     IndexBinaryFlat,
+    IndexFlat,
     IndexFlatIP,
     IndexFlatL2,
     IndexIVFFlat,

@@ -175,6 +175,24 @@ SIGNATURES = {
     "ivfpq_bin_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int), c_i64p, c_i64p]),
+    # flat fp32 rows (IndexFlat / IndexFlatL2 / IndexFlatIP)
+    "ivfpq_flat_index_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_handle)]),
+    "ivfpq_flat_index_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_flat_index_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_flat_index_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
+    "ivfpq_flat_index_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_flat_index_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_flat_index_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_flat_index_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_flat_index_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "ivfpq_flat_index_get_rows": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_f32p]),
+    "ivfpq_flat_index_get_stats": (ctypes.c_int, [c_handle, c_i64p, c_i64p, c_i64p]),
+    "ivfpq_flat_index_set_range_rows": (ctypes.c_int, [c_handle, ctypes.c_int64]),
+    "ivfpq_flat_index_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                                 ctypes.POINTER(ctypes.c_int), c_i64p, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_int), c_i64p]),
 }
 
 

@@ -49,6 +49,15 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
     "IxPT" may wrap it too.
     Unpinned like the others: no Faiss-written "IxSQ" file exists on the build machine.
 
+    "IxF2" (L2) | "IxFI" (IP)                IndexFlatL2 / IndexFlatIP as a file of its own (beir
+                                             faiss_index.py:29 save / load of the FlatIP index of
+                                             faiss_search.py:337)
+      index header
+      xb = u64 count + f32[ntotal * d]
+    The record the IVF files embed as their quantizer; an IndexFlat(d, metric) is written under the
+    fourcc of its metric and read back as IndexFlatL2 / IndexFlatIP, as Faiss does.
+    Unpinned like the others: no Faiss-written "IxF2" / "IxFI" file exists on the build machine.
+
     "IBxF"                                   IndexBinaryFlat (beir faiss_search.py BinaryFaissSearch;
                                              written by write_index_binary, read by read_index_binary)
       d i32 (bits), code_size i32 (d / 8), ntotal i64, is_trained u8, metric_type i32 (1)
@@ -83,7 +92,8 @@ FOURCC_LINEAR = b"LTra"
 
 def is_faiss_file(path) -> bool:
     with open(path, "rb") as f:
-        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT, FOURCC_SQ)
+        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT, FOURCC_SQ,
+                             FOURCC_FLAT[0], FOURCC_FLAT[1])
 
 
 class _Reader:
@@ -136,10 +146,13 @@ def parse_index(buf: bytes) -> dict:
     IVF-PQ -> parse_ivfpq's dict with kind "ivfpq"; pre-transform -> {kind
     "pretransform", d, ntotal, metric, chain: [{A [d_out][d_in], b, have_bias,
     d_in, d_out, is_trained}], index: the IVF-PQ dict}; IndexPQ -> kind "pq";
-    IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat); IndexScalarQuantizer -> kind "sq" (_parse_sq)."""
+    IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat); IndexScalarQuantizer -> kind "sq" (_parse_sq);
+    a top-level IndexFlatL2 / IndexFlatIP -> kind "flat" (_parse_flat)."""
     r = _Reader(buf)
     h = r.fourcc()
-    if h == FOURCC_PRETRANSFORM:
+    if h in FOURCC_FLAT.values():
+        z = _parse_flat(r, h)
+    elif h == FOURCC_PRETRANSFORM:
         d, ntotal, is_trained, metric = r.header()
         nt = r.fmt("i")
         chain = [_parse_linear(r) for _ in range(nt)]
@@ -162,6 +175,33 @@ def _parse_sub(r: "_Reader", h: bytes) -> dict:
     if h == FOURCC_SQ:
         return _parse_sq(r)
     return _parse_pq(r) if h == FOURCC_PQ else _parse_ivfpq(r, h)
+
+
+def _parse_flat(r: "_Reader", h: bytes) -> dict:
+    """IndexFlatL2 / IndexFlatIP after its fourcc -> {kind "flat", d, ntotal, metric, is_trained,
+    xb f32 [ntotal][d]}; the metric is the fourcc's, which the header must repeat."""
+    metric = 1 if h == FOURCC_FLAT[1] else 0
+    d, ntotal, is_trained, hm = r.header()
+    xb = r.vector(np.float32)
+    if d <= 0 or ntotal < 0:
+        raise RuntimeError(f"IndexFlat header is invalid (d = {d}, ntotal = {ntotal})")
+    if hm != metric:
+        raise RuntimeError(f"IndexFlat fourcc {h!r} does not match metric_type {hm}")
+    if xb.size != ntotal * d:
+        raise RuntimeError(f"IndexFlat xb holds {xb.size} floats, ntotal * d = {ntotal * d}")
+    return {"kind": "flat", "d": d, "ntotal": ntotal, "metric": metric, "is_trained": is_trained,
+            "xb": xb.reshape(ntotal, d)}
+
+
+def serialize_flat(d, metric, xb) -> bytes:
+    """The inverse of parse_index for kind "flat": xb float32 [ntotal][d].
+    Unpinned against Faiss, like the other layouts (see the module docstring)."""
+    if metric not in FOURCC_FLAT:
+        raise RuntimeError(f"IndexFlat: unknown metric {metric}")
+    xb = np.ascontiguousarray(xb, np.float32).reshape(-1)
+    if d <= 0 or xb.size % d:
+        raise RuntimeError(f"xb must hold whole rows of {d} floats")
+    return b"".join([FOURCC_FLAT[metric], _header(d, xb.size // d, True, metric), _vector(xb)])
 
 
 def _parse_pq(r: "_Reader") -> dict:

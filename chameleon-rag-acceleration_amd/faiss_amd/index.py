@@ -21,7 +21,9 @@ The surface mirrors what Chameleon's callers use on ``faiss`` (SURVEY.md
 * ``IndexBinaryFlat(d)`` with ``index_binary_factory``, ``write_index_binary`` and
   ``read_index_binary`` (beir ``faiss_search.py:134-166`` BinaryFaissSearch through
   ``faiss_index.py:98-174`` FaissBinaryIndex: Hamming candidates, then a float re-rank);
-* ``IndexFlatL2`` (the coarse quantizer; exact search on the GPU);
+* ``IndexFlat(d, metric)``, ``IndexFlatL2``, ``IndexFlatIP`` (the coarse quantizer; standalone,
+  exact search over device-resident rows: beir ``faiss_index.py:39-42``, ``faiss_search.py:337``;
+  ``bench_gpu_1bn.py:444-455``; ``ralm/index_scanner/index_scanner.py:34-77``);
 * ``index_factory``, ``ParameterSpace``, ``read_index / write_index``,
   ``swig_ptr``, ``vector_to_array``, ``get_num_gpus``.
 
@@ -89,56 +91,211 @@ def _default_device():
     return 0
 
 
-class IndexFlatL2:
-    """Exact L2 search (faiss.IndexFlatL2).  As an IVF quantizer it holds the
-    coarse centroids (``quantizer.xb``, extract_FPGA_required_data.py:174-184);
-    standalone, ``search`` runs the GPU distance + select kernels (the
-    IndexScanner coarse service, ralm/index_scanner/index_scanner.py:61-77)."""
+class IndexFlat:
+    """Exact search over the raw vectors (faiss.IndexFlat(d, metric)): L2 returns the k
+    smallest distances ascending, inner product the k largest descending, ties by label (the
+    row position), missing results (FLT_MAX | -FLT_MAX, -1).
 
-    metric_type = METRIC_L2
+    Two roles share the class.  As an IVF quantizer it only holds the coarse centroids
+    (``quantizer.xb``, extract_FPGA_required_data.py:174-184): ``add``, ``reset``, ``xb``,
+    ``reconstruct``, ``reconstruct_n`` and ``ntotal`` work on a host buffer that grows
+    geometrically and need neither a GPU nor the library.  Standalone (beir
+    faiss_index.py:39-42 FlatIP, the IndexScanner coarse service of
+    ralm/index_scanner/index_scanner.py:61-77, the ground truth of bench_gpu_1bn.py:444-455)
+    the rows are resident in HBM: the device image is created at the first device use and
+    extended from the rows not yet uploaded, ``add_device`` appends to it directly, and the
+    host accessors fetch the rows the host has not seen.  ``search`` runs the fused
+    matrix-core scan over the image (csrc/flat_scan.hip); its results are those of the
+    stateless ``ivfpq_flat_search`` bit for bit."""
+
     is_trained = True
 
-    def __init__(self, d, device=None):
+    def __init__(self, d, metric=METRIC_L2, device=None):
+        d = int(d)  # (d >= 1 is checked where the device image is created: an IVF index validates its own d)
+        if metric not in (METRIC_L2, METRIC_INNER_PRODUCT):
+            raise RuntimeError(f"IndexFlat: unknown metric {metric}")
         self.d = d
-        self.device = _default_device() if device is None else device
-        self._xb = np.zeros((0, d), np.float32)
+        self.metric_type = metric
+        self.device = _default_device() if device is None else int(device)
+        self.verbose = False
+        self._h = None
+        self._buf = np.empty((0, max(d, 0)), np.float32)  # host rows [0, _nhost); _buf.shape[0] is the capacity
+        self._nhost = 0   # rows the host buffer holds (a prefix of the index)
+        self._ndev = 0    # rows the device image holds (a prefix of the index)
+        self._ntotal = 0
+        self._range_rows = 0
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ivfpq_flat_index_free(h)
+            self._h = None
 
     @property
     def ntotal(self):
-        return self._xb.shape[0]
+        return self._ntotal
+
+    @property
+    def capacity(self):
+        """Rows the host buffer has room for (it doubles when full)."""
+        return self._buf.shape[0]
+
+    # -------------------------------------------------------------- host rows
+    def _host_reserve(self, n):
+        need = self._nhost + n
+        if need <= self._buf.shape[0]:
+            return
+        buf = np.empty((max(need, 2 * self._buf.shape[0], 64), self.d), np.float32)
+        buf[:self._nhost] = self._buf[:self._nhost]
+        self._buf = buf
+
+    def _sync_host(self):
+        """Fetch the rows only the device image holds (after add_device)."""
+        n = self._ntotal - self._nhost
+        if n <= 0:
+            return
+        self._host_reserve(n)
+        out = self._buf[self._nhost:self._ntotal]
+        _lib.check(_lib.load().ivfpq_flat_index_get_rows(self._h, self._nhost, n, _ptr(out, _lib.c_f32p)))
+        self._nhost = self._ntotal
+
+    def _sync_device(self):
+        """Create the device image at its first use and upload the rows it lacks."""
+        L = _lib.load()
+        if self._h is None:
+            h = _lib.c_handle()
+            _lib.check(L.ivfpq_flat_index_create(self.device, self.d, self.metric_type, ctypes.byref(h)))
+            self._h = h
+            self._ndev = 0
+            if self._range_rows:
+                _lib.check(L.ivfpq_flat_index_set_range_rows(h, self._range_rows))
+        n = self._ntotal - self._ndev
+        if n > 0:
+            rows = self._buf[self._ndev:self._ntotal]
+            _lib.check(L.ivfpq_flat_index_add(self._h, n, _ptr(rows, _lib.c_f32p)))
+            self._ndev = self._ntotal
+        return L
 
     @property
     def xb(self):
-        return self._xb.reshape(-1)
+        self._sync_host()
+        return self._buf[:self._ntotal].reshape(-1)
 
     def add(self, x):
         x = _f32(x, self.d)
-        self._xb = np.concatenate([self._xb, x]) if self.ntotal else x.copy()
+        self._sync_host()
+        self._host_reserve(x.shape[0])
+        self._buf[self._nhost:self._nhost + x.shape[0]] = x
+        self._nhost += x.shape[0]
+        self._ntotal = self._nhost
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
+
+    def add_device(self, x, stream=None):
+        """add with the vectors already in HBM (torch float32 CUDA tensor [n, d]): appended
+        straight to the device image; returns once the rows are in place."""
+        import torch
+
+        n = x.shape[0] if x.dim() == 2 else -1
+        self._check_dev(x, "x", torch.float32, (n, self.d))
+        L = self._sync_device()
+        _lib.check(L.ivfpq_flat_index_add_device(self._h, n, x.data_ptr(),
+                                                 ctypes.c_void_p(self._stream(x, stream))))
+        self._ntotal += n
+        self._ndev = self._ntotal
 
     def reset(self):
-        self._xb = np.zeros((0, self.d), np.float32)
+        if self._h is not None:
+            _lib.check(_lib.load().ivfpq_flat_index_reset(self._h))
+        self._buf = np.empty((0, self.d), np.float32)
+        self._nhost = self._ndev = self._ntotal = 0
 
     def reconstruct(self, i):
-        return self._xb[i].copy()
+        i = int(i)
+        if not 0 <= i < self._ntotal:
+            raise RuntimeError(f"reconstruct: {i} outside [0, {self._ntotal})")
+        self._sync_host()
+        return self._buf[i].copy()
 
     def reconstruct_n(self, i0, n):
-        return self._xb[i0:i0 + n].copy()
+        self._sync_host()
+        return self._buf[i0:min(i0 + n, self._ntotal)].copy()
 
     def train(self, x):
         pass
 
+    def set_range_rows(self, rows):
+        """The base rows one scan workgroup takes (0 = chosen per search so that the grid
+        fills the device).  Results do not depend on it; tests use it to cut small bases into
+        several ranges (``flat_search_plan`` tells the split)."""
+        rows = int(rows)
+        if rows < 0:
+            raise RuntimeError("negative range size")
+        self._range_rows = rows
+        if self._h is not None:
+            _lib.check(_lib.load().ivfpq_flat_index_set_range_rows(self._h, rows))
+
+    def uploaded_rows(self):
+        """Rows copied from the host into the device image since it was created (the image is
+        extended, not rebuilt: every row counts once)."""
+        if self._h is None:
+            return 0
+        out = ctypes.c_int64(0)
+        _lib.check(_lib.load().ivfpq_flat_index_get_stats(self._h, ctypes.byref(out), None, None))
+        return out.value
+
+    # ------------------------------------------------------------ search path
     def search(self, x, k):
         x = _f32(x, self.d)
         n = x.shape[0]
-        if not 1 <= k <= MAX_K:
+        if not 1 <= int(k) <= MAX_K:
             raise RuntimeError(f"k must be in [1, {MAX_K}]")
         D = np.empty((n, k), np.float32)
         I = np.empty((n, k), np.int64)
-        L = _lib.load()
-        _lib.check(L.ivfpq_flat_search(self.device, self.d, self.ntotal, _ptr(self._xb, _lib.c_f32p), n,
-                                       _ptr(x, _lib.c_f32p), k, self.metric_type, _ptr(D, _lib.c_f32p),
-                                       _ptr(I, _lib.c_i64p)))
+        L = self._sync_device()
+        _lib.check(L.ivfpq_flat_index_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
+                                             _ptr(I, _lib.c_i64p)))
         return D, I
+
+    def search_device(self, x, k, D=None, I=None, stream=None):
+        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
+        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
+        import torch
+
+        self._check_k(k)
+        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
+        D, I = self._dev_outputs(x, k, D, I)
+        L = self._sync_device()
+        _lib.check(L.ivfpq_flat_index_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
+                                                    I.data_ptr(),
+                                                    ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+
+def flat_search_plan(nq, nb, k, range_rows=0):
+    """How an IndexFlat search of nq queries for k results over nb rows is split
+    (ivfpq_flat_index_get_plan; host arithmetic, no device): dict of tile_q, range_rows,
+    ranges, S, fan, rounds, query_chunk."""
+    ints = {n: ctypes.c_int() for n in ("tile_q", "ranges", "S", "fan", "rounds")}
+    rows, qc = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(_lib.load().ivfpq_flat_index_get_plan(int(nq), int(nb), int(k), int(range_rows),
+                                                     ctypes.byref(ints["tile_q"]), ctypes.byref(rows),
+                                                     ctypes.byref(ints["ranges"]), ctypes.byref(ints["S"]),
+                                                     ctypes.byref(ints["fan"]), ctypes.byref(ints["rounds"]),
+                                                     ctypes.byref(qc)))
+    out = {n: v.value for n, v in ints.items()}
+    out.update(range_rows=rows.value, query_chunk=qc.value)
+    return out
+
+
+class IndexFlatL2(IndexFlat):
+    """faiss.IndexFlatL2(d): IndexFlat with the L2 metric (the default coarse quantizer)."""
+
+    metric_type = METRIC_L2
+
+    def __init__(self, d, device=None):
+        IndexFlat.__init__(self, d, type(self).metric_type, device)
 
 
 class IndexFlatIP(IndexFlatL2):
@@ -654,6 +811,12 @@ class IndexIVFPQ:
                                                           x_tables.data_ptr(), ctypes.c_void_p(self._stream(x, stream)),
                                                           ctypes.byref(tok)))
         return Dq, Iq, tok.value
+
+
+# the device-argument checks of the flat index (defined above IndexIVFPQ) are IndexIVFPQ's
+for _name in ("_check_k", "_check_dev", "_dev_outputs", "_stream"):
+    setattr(IndexFlat, _name, getattr(IndexIVFPQ, _name))
+del _name
 
 
 class IndexPQ:
@@ -1379,9 +1542,12 @@ def index_factory(d, key, metric=METRIC_L2, device=None):
     OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), the flat
     "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
     "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
-    truth of compute_ground_truth.py:311), and the flat scalar quantizers "SQ8" / "SQfp16"."""
+    truth of compute_ground_truth.py:311), the flat scalar quantizers "SQ8" / "SQfp16", and
+    "Flat" (an IndexFlat of the given metric: beir faiss_search.py:337)."""
     from .transform import IndexPreTransform, OPQMatrix
 
+    if key.replace(" ", "") == "Flat":
+        return IndexFlat(d, metric, device)
     qtype = parse_sq_factory(key)
     if qtype is not None:
         return IndexScalarQuantizer(d, qtype, metric, device)
@@ -1451,6 +1617,10 @@ def _sq_bytes(index):
                                  index._codes(0, index.ntotal))
 
 
+def _flat_bytes(index):
+    return faiss_io.serialize_flat(index.d, index.metric_type, index.xb.reshape(-1, index.d))
+
+
 def _sub_bytes(index):
     if isinstance(index, IndexScalarQuantizer):
         return _sq_bytes(index)
@@ -1459,7 +1629,7 @@ def _sub_bytes(index):
 
 def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
-    IndexIVFFlat / IndexScalarQuantizer / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
+    IndexIVFFlat / IndexScalarQuantizer / IndexFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform
 
@@ -1469,6 +1639,10 @@ def write_index(index, path, fmt="faiss"):
         chain = [(t.A, t.b, t.d_in, t.d_out, t.is_trained) for t in index.chain]
         buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, _sub_bytes(index.index),
                                               index.ntotal)
+    elif isinstance(index, IndexFlat):
+        if fmt != "faiss":
+            raise RuntimeError("IndexFlat is written in the Faiss layout")
+        buf = _flat_bytes(index)
     elif isinstance(index, IndexPQ):
         if fmt != "faiss":
             raise RuntimeError("IndexPQ is written in the Faiss layout")
@@ -1536,7 +1710,17 @@ def _sq_from_dict(z, device):
     return idx
 
 
+def _flat_from_dict(z, device):
+    cls = {METRIC_L2: IndexFlatL2, METRIC_INNER_PRODUCT: IndexFlatIP}[z["metric"]]
+    idx = cls(z["d"], device)
+    if z["ntotal"]:
+        idx.add(z["xb"])
+    return idx
+
+
 def _index_from_dict(z, device):
+    if z["kind"] == "flat":
+        return _flat_from_dict(z, device)
     if z["kind"] == "ivfflat":
         return _ivfflat_from_dict(z, device)
     if z["kind"] == "sq":
@@ -1545,7 +1729,7 @@ def _index_from_dict(z, device):
 
 
 def read_index(path, device=None):
-    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexScalarQuantizer ("IxSQ") / IndexPreTransform ("IxPT")
+    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexScalarQuantizer ("IxSQ") / IndexFlatL2 ("IxF2") / IndexFlatIP ("IxFI") / IndexPreTransform ("IxPT")
     file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
     with open(path, "rb") as f:

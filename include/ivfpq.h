@@ -420,6 +420,54 @@ int ivfpq_bin_get_codes(ivfpq_bin_index* h, int64_t i0, int64_t n, uint8_t* out)
 int ivfpq_bin_get_plan(int d, int64_t ntotal, int64_t nq, int k, int* stride, int* query_block, int* segments,
                        int64_t* segment_rows, int64_t* query_chunk);
 
+/* ---- flat fp32 rows: faiss.IndexFlat(d, metric) / IndexFlatL2 / IndexFlatIP -----------
+ * (beir faiss_index.py:39-42 and faiss_search.py:337 FlatIPFaissSearch; the ground truth of
+ * bench_gpu_1bn.py:444-455; the coarse service of ralm/index_scanner/index_scanner.py:34-77).
+ * The rows are resident in HBM, [ntotal][d] fp32, with their squared norms beside them
+ * (computed once, at add); nothing is trained; the label of a row is its position.  search
+ * is exact: distances, order, ties and padding are ivfpq_flat_search's bit for bit -- L2
+ * max(0, (|x|^2 + |y|^2) - 2 <x, y>) ascending, inner product <x, y> descending, <x, y> one
+ * ascending chain of fused multiply-adds, ties by label, (FLT_MAX | -FLT_MAX, -1) where fewer
+ * than k rows exist.  A search is one fused matrix-core scan with the top-k in registers
+ * (csrc/flat_scan.h; no distance reaches memory) and the merge of its partial lists.  Any
+ * d >= 1; 1 <= k <= 1024; at most 2^31 - 2
+ * rows.  The arguments are checked before any device call.  Same conventions, errors and
+ * locking as above (one mutex per handle); device calls of one handle on different streams
+ * run one after the other. */
+typedef struct ivfpq_flat_index ivfpq_flat_index;
+
+int ivfpq_flat_index_create(int device, int d, int metric, ivfpq_flat_index** out);
+int ivfpq_flat_index_free(ivfpq_flat_index* h); /* free(NULL) returns 0 */
+/* Index.reset(): drop the rows. */
+int ivfpq_flat_index_reset(ivfpq_flat_index* h);
+/* Index.add(x): appended to the device row image, which grows geometrically (O(rows added)). */
+int ivfpq_flat_index_add(ivfpq_flat_index* h, int64_t n, const float* x);
+/* The same with x in HBM, on `stream` (hipStream_t, NULL = default); returns when the rows are in place. */
+int ivfpq_flat_index_add_device(ivfpq_flat_index* h, int64_t n, const float* x, void* stream);
+/* Index.search(x, k) -> (D, I), host buffers / device pointers on `stream`. */
+int ivfpq_flat_index_search(ivfpq_flat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I);
+int ivfpq_flat_index_search_device(ivfpq_flat_index* h, int64_t n, const float* x, int k, float* D, int64_t* I,
+                                   void* stream);
+int64_t ivfpq_flat_index_ntotal(const ivfpq_flat_index* h);
+int ivfpq_flat_index_get_dims(const ivfpq_flat_index* h, int* d, int* metric);
+/* rows [i0, i0 + n) to the host, float [n][d] (IndexFlat.xb / reconstruct_n) */
+int ivfpq_flat_index_get_rows(ivfpq_flat_index* h, int64_t i0, int64_t n, float* out);
+/* Bookkeeping of the image (outputs nullable): rows copied from the host since create, rows
+ * allocated, times the image was reallocated. */
+int ivfpq_flat_index_get_stats(ivfpq_flat_index* h, int64_t* rows_from_host, int64_t* capacity, int64_t* reallocs);
+/* The row range one scan workgroup of the fused path takes: rows > 0 sets it (rounded up to the
+ * scan's row tile, kFlatTileRows of csrc/flat_scan.h), 0 (default) lets every search pick the
+ * number of ranges that fills the device.  Results do not depend on it; the test suite uses it
+ * to reach several ranges and several merge rounds with small shapes (include/ivfpq_test.h). */
+int ivfpq_flat_index_set_range_rows(ivfpq_flat_index* h, int64_t rows);
+/* The plan of a search of nq queries for k results over nb rows with that setting (no handle,
+ * no device call): tile_q = the queries a scan workgroup takes (64; 16 for batches of at most
+ * 16 queries and for k > 256); ranges x range_rows = the row ranges of a chunk of
+ * min(nq, query_chunk) queries, S = the sorted partial lists per query in the workspace
+ * (>= ranges), merged `fan` at a time in `rounds` rounds.  Outputs are nullable. */
+int ivfpq_flat_index_get_plan(int64_t nq, int64_t nb, int k, int64_t set_rows, int* tile_q, int64_t* range_rows,
+                              int* ranges, int* S, int* fan, int* rounds, int64_t* query_chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """IndexIVFFlat throughput on one MI355X beside its two bounds, and the paired comparison
-with the library's other exact-distance search (IndexFlatL2.search = ivfpq_flat_search:
-brute force, the full distance matrix written and selected from).
+with the library's other exact-distance search, IndexFlatL2.search.
+
+What the comparator measures changed with the device-resident flat index: IndexFlatL2.search
+no longer is ivfpq_flat_search (brute force with the base uploaded on every call and the full
+distance matrix written and selected from -- what profiles/ivfflat_bench.json and DESIGN.md
+section 4c recorded) but the fused scan over rows kept in HBM, whose
+first call also uploads the rows.  A new run of this script therefore compares IndexIVFFlat
+with the resident flat index; profiles/indexflat_bench.py times the stateless call, IVF1,Flat
+and the flat index in one job.
 
     python profiles/ivfflat_bench.py [--out profiles/ivfflat_bench.json] [--nb 1000000]
 
@@ -16,8 +23,8 @@ quantizer, planning, scan, merge) after a warm-up, over a window of at least a s
 The comparator takes host buffers only, so each of the three alternating pairs times one
 host call of each side with the wall clock (``IndexIVFFlat.search`` against
 ``IndexFlatL2.search`` of the same queries over the same vectors; both copy the queries
-in and the results out, the comparator also uploads the base vectors, which it does not
-keep).  Bounds, from the batch's own probes:
+in and the results out; the comparator uploads the base vectors in its first call and keeps
+them).  Bounds, from the batch's own probes:
   valu_floor_ms   3 d (rows scanned x queries served) lane-operations (subtract, multiply,
                   add; -ffp-contract=off) over 256 CUs x 128 lanes x 2.4 GHz
   hbm_floor_ms    list bytes fetched once per (row range, group of G pairs) over the HBM

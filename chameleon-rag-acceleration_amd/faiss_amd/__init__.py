@@ -38,6 +38,7 @@ from .transform import (  # noqa: F401
     IndexPreTransform,
     LinearTransform,
     OPQMatrix,
+    PCAMatrix,
     downcast_VectorTransform,
     read_VectorTransform,
     write_VectorTransform,

@@ -78,6 +78,12 @@ SIGNATURES = {
     "ivfpq_linear_transform_device": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_void_p]),
+    # PCA training moments (PCAMatrix.train), their chunk setting and plan
+    "ivfpq_pca_moments_device": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_pca_set_chunk_rows": (ctypes.c_int, [ctypes.c_int64]),
+    "ivfpq_pca_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), c_i64p,
+                                          ctypes.POINTER(ctypes.c_int)]),
     "ivfpq_set_timing": (ctypes.c_int, [c_handle, ctypes.c_int]),
     "ivfpq_get_timing": (ctypes.c_int, [c_handle, ctypes.POINTER(ctypes.c_double), c_i64p]),
     "ivfpq_ntotal": (ctypes.c_int64, [c_handle]),

@@ -27,8 +27,14 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
       VectorTransform "LTra" (LinearTransform, and OPQMatrix, which Faiss writes as a plain
       LinearTransform): have_bias u8, A = u64 count + f32[d_out * d_in], b = u64 count + f32[count],
       d_in i32, d_out i32, is_trained u8
+      VectorTransform "PcAm" (PCAMatrix; beir faiss_search.py:359-413, the "PCAR<dout>," front of
+      bench_gpu_1bn.py:490-492): eigen_power f32, random_rotation u8, balanced_bins i32,
+      mean = u64 count + f32[d_in], eigenvalues = u64 count + f32[d_in], PCAMat = u64 count +
+      f32[d_in * d_in], then the "LTra" body above from have_bias on.  The 1.7.1 layout: later
+      Faiss versions insert an epsilon f32 after eigen_power.  The wrapped index may also be an
+      "IxF2" / "IxFI" flat index (beir's PCAFaissSearch over IndexFlatIP).
 
-    "IxPq"                                   IndexPQ (beir faiss_search.py:168-224)
+    "IxPq"                                  IndexPQ (beir faiss_search.py:168-224)
       index header
       PQ:          d u64, M u64, nbits u64, centroids = u64 count + f32[count]   ([M][ksub][dsub])
       codes = u64 count + u8[ntotal * code_size]
@@ -88,6 +94,7 @@ HEADER_DUMMY = 1 << 20
 
 FOURCC_PRETRANSFORM = b"IxPT"
 FOURCC_LINEAR = b"LTra"
+FOURCC_PCA = b"PcAm"
 
 
 def is_faiss_file(path) -> bool:
@@ -170,6 +177,8 @@ def parse_index(buf: bytes) -> dict:
 
 
 def _parse_sub(r: "_Reader", h: bytes) -> dict:
+    if h in FOURCC_FLAT.values():
+        return _parse_flat(r, h)
     if h == FOURCC_IVFFLAT:
         return _parse_ivfflat(r)
     if h == FOURCC_SQ:
@@ -328,9 +337,34 @@ def serialize_binary_flat(d, codes) -> bytes:
 
 
 def _parse_linear(r: _Reader) -> dict:
+    """One VectorTransform record: "LTra" -> the LinearTransform dict; "PcAm" -> the same dict
+    with kind "pca" and eigen_power, random_rotation, balanced_bins, mean [d_in], eigenvalues
+    [d_in], PCAMat [d_in][d_in] (rows are eigenvectors)."""
     vh = r.fourcc()
+    if vh == FOURCC_PCA:
+        try:
+            head = {"kind": "pca", "eigen_power": r.fmt("f"), "random_rotation": r.fmt("B") != 0,
+                    "balanced_bins": r.fmt("i"), "mean": r.vector(np.float32), "eigenvalues": r.vector(np.float32),
+                    "PCAMat": r.vector(np.float32)}
+            t = _parse_linear_body(r)
+        except RuntimeError as e:  # (the fields of another record, or of a later layout, read as counts)
+            raise RuntimeError(f"malformed {FOURCC_PCA!r} VectorTransform record: {e}") from None
+        d = t["d_in"]
+        if t["is_trained"] and (head["mean"].size != d or head["eigenvalues"].size != d
+                                or head["PCAMat"].size != d * d):
+            raise RuntimeError("PCAMatrix mean / eigenvalues / PCAMat have the wrong size")
+        if head["PCAMat"].size == d * d:
+            head["PCAMat"] = head["PCAMat"].reshape(d, d)
+        t.update(head)
+        return t
     if vh != FOURCC_LINEAR:
-        raise RuntimeError(f"unsupported VectorTransform {vh!r} (LinearTransform / OPQMatrix only)")
+        raise RuntimeError(f"unsupported VectorTransform {vh!r} (LinearTransform / OPQMatrix {FOURCC_LINEAR!r}, "
+                           f"PCAMatrix {FOURCC_PCA!r} only)")
+    return _parse_linear_body(r)
+
+
+def _parse_linear_body(r: _Reader) -> dict:
+    """What "LTra" writes after its fourcc (and "PcAm" after its own fields)."""
     have_bias = r.fmt("B") != 0
     A = r.vector(np.float32)
     b = r.vector(np.float32)
@@ -346,7 +380,7 @@ def _parse_linear(r: _Reader) -> dict:
 
 
 def parse_vector_transform(buf: bytes) -> dict:
-    """A faiss.write_VectorTransform file (bench_gpu_1bn.py:507-510): one "LTra" record."""
+    """A faiss.write_VectorTransform file (bench_gpu_1bn.py:507-510): one "LTra" or "PcAm" record."""
     r = _Reader(buf)
     t = _parse_linear(r)
     if r.o != len(r.b):
@@ -359,6 +393,21 @@ def serialize_linear(A, b, d_in, d_out, is_trained=True) -> bytes:
     bb = np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(-1)
     return b"".join([FOURCC_LINEAR, struct.pack("<B", 0 if b is None else 1), _vector(A), _vector(bb),
                      struct.pack("<iiB", d_in, d_out, 1 if is_trained else 0)])
+
+
+def serialize_pca(eigen_power, random_rotation, balanced_bins, mean, eigenvalues, PCAMat, A, b, d_in, d_out,
+                  is_trained=True) -> bytes:
+    """A PCAMatrix as Faiss 1.7.1 writes it: "PcAm", eigen_power f32, random_rotation u8,
+    balanced_bins i32, the vectors mean, eigenvalues, PCAMat, then the LinearTransform body
+    exactly as "LTra" has it after its fourcc.  (Later Faiss versions insert an ``epsilon``
+    f32 after eigen_power: this is the layout without it.)  Unpinned against Faiss, like the
+    other layouts (see the module docstring)."""
+    def vec(a):
+        return _vector(np.zeros(0, np.float32) if a is None else np.ascontiguousarray(a, np.float32).reshape(-1))
+
+    return b"".join([FOURCC_PCA, struct.pack("<fBi", eigen_power, 1 if random_rotation else 0, balanced_bins),
+                     vec(mean), vec(eigenvalues), vec(PCAMat),
+                     serialize_linear(A, b, d_in, d_out, is_trained)[4:]])
 
 
 def _parse_ivfpq(r: _Reader, h: bytes) -> dict:
@@ -496,9 +545,10 @@ def _ilar(nlist, code_size, lists):
 
 
 def serialize_pretransform(d, metric, chain, sub: bytes, ntotal, is_trained=True) -> bytes:
-    """IndexPreTransform bytes: chain = [(A [d_out][d_in] | None, b | None, d_in, d_out, is_trained)],
+    """IndexPreTransform bytes: chain = [(A [d_out][d_in] | None, b | None, d_in, d_out, is_trained)
+    | the bytes of one VectorTransform record (serialize_linear, serialize_pca)],
     sub = the wrapped index's bytes (serialize_ivfpq)."""
     out = [FOURCC_PRETRANSFORM, _header(d, ntotal, is_trained, metric), struct.pack("<i", len(chain))]
-    out += [serialize_linear(*t) for t in chain]
+    out += [t if isinstance(t, bytes) else serialize_linear(*t) for t in chain]
     out.append(sub)
     return b"".join(out)

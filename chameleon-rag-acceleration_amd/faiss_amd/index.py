@@ -1479,6 +1479,7 @@ _FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x(\d+))?
 _IVFFLAT_FACTORY_RE = re.compile(r"^IVF(\d+),Flat$")
 _SQ_FACTORY_RE = re.compile(r"^SQ(\w+)$")
 _SQ_FACTORY_TYPES = {"8": ScalarQuantizer.QT_8bit, "fp16": ScalarQuantizer.QT_fp16}
+_PCA_FRONT_RE = re.compile(r"^PCA(W?)(R?)(\d+),(.+)$")
 
 
 def parse_factory(key):
@@ -1487,7 +1488,8 @@ def parse_factory(key):
     m = _FACTORY_RE.match(key.replace(" ", ""))
     if not m:
         raise RuntimeError(f"index_factory: unsupported key {key!r} "
-                           "(supported: '[OPQ<M>[_<dout>],]IVF<nlist>,PQ<M>[x8]')")
+                           "(supported: '[OPQ<M>[_<dout>],]IVF<nlist>,PQ<M>[x8]', '[OPQ<M>[_<dout>],]PQ<M>[x8]', "
+                           "'IVF<nlist>,Flat', 'SQ8', 'SQfp16', 'Flat', each also behind a 'PCA[W][R]<dout>,' front)")
     nbits = int(m.group(5)) if m.group(5) else 8
     base = (int(m.group(3)), int(m.group(4)), nbits)
     if m.group(1) is None:
@@ -1505,6 +1507,20 @@ def parse_pq_factory(key):
     if m.group(1) is None:
         return base
     return base + (int(m.group(1)), int(m.group(2)) if m.group(2) else -1)
+
+
+def parse_pca_front(key):
+    """'PCA[W][R]<dout>,<rest>' -> (dout, eigen_power, random_rotation, rest): W whitens
+    (eigen_power = -0.5), R adds the random rotation; None for a key that does not start with
+    'PCA'; any other 'PCA...' front raises, naming the key."""
+    key = key.replace(" ", "")
+    if not key.startswith("PCA"):
+        return None
+    m = _PCA_FRONT_RE.match(key)
+    if not m:
+        raise RuntimeError(f"index_factory: unsupported key {key!r} (a PCA front is 'PCA<dout>,', 'PCAR<dout>,', "
+                           "'PCAW<dout>,' or 'PCAWR<dout>,' before a supported key)")
+    return int(m.group(3)), -0.5 if m.group(1) else 0.0, bool(m.group(2)), m.group(4)
 
 
 def parse_ivfflat_factory(key):
@@ -1543,9 +1559,20 @@ def index_factory(d, key, metric=METRIC_L2, device=None):
     "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
     "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
     truth of compute_ground_truth.py:311), the flat scalar quantizers "SQ8" / "SQfp16", and
-    "Flat" (an IndexFlat of the given metric: beir faiss_search.py:337)."""
-    from .transform import IndexPreTransform, OPQMatrix
+    "Flat" (an IndexFlat of the given metric: beir faiss_search.py:337).  Each may stand behind
+    a PCA front, "PCA<dout>," / "PCAR<dout>," / "PCAW<dout>," / "PCAWR<dout>," (bench_gpu_1bn.py:
+    490-492): IndexPreTransform(PCAMatrix(d, dout, ...), the rest built at dout)."""
+    from .transform import IndexPreTransform, OPQMatrix, PCAMatrix
 
+    front = parse_pca_front(key)
+    if front is not None:
+        dout, eigen_power, rotate, rest = front
+        pca = PCAMatrix(d, dout, eigen_power, rotate)
+        pca._check_trainable()  # (dout > d raises here, naming both)
+        inner = index_factory(dout, rest, metric, device)
+        if isinstance(inner, IndexPreTransform):  # "PCA64,OPQ16,IVF..": one chain
+            return IndexPreTransform([pca] + list(inner.chain), inner.index)
+        return IndexPreTransform(pca, inner)
     if key.replace(" ", "") == "Flat":
         return IndexFlat(d, metric, device)
     qtype = parse_sq_factory(key)
@@ -1622,6 +1649,10 @@ def _flat_bytes(index):
 
 
 def _sub_bytes(index):
+    if isinstance(index, IndexFlat):
+        return _flat_bytes(index)
+    if isinstance(index, IndexIVFFlat):
+        return _ivfflat_bytes(index)
     if isinstance(index, IndexScalarQuantizer):
         return _sq_bytes(index)
     return _pq_bytes(index) if isinstance(index, IndexPQ) else _ivfpq_bytes(index)
@@ -1631,12 +1662,12 @@ def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
     IndexIVFFlat / IndexScalarQuantizer / IndexFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
-    from .transform import IndexPreTransform
+    from .transform import IndexPreTransform, _transform_bytes
 
     if isinstance(index, IndexPreTransform):
         if fmt != "faiss" or not index.is_trained:
             raise RuntimeError("IndexPreTransform is written in the Faiss layout once trained")
-        chain = [(t.A, t.b, t.d_in, t.d_out, t.is_trained) for t in index.chain]
+        chain = [_transform_bytes(t) for t in index.chain]
         buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, _sub_bytes(index.index),
                                               index.ntotal)
     elif isinstance(index, IndexFlat):

@@ -18,10 +18,16 @@ back out of the index (``my_faiss_extract_scripts/extract_FPGA_required_data.py:
   decode, orthogonal Procrustes by SVD).  It runs on the host in numpy/float64
   like Faiss's LAPACK path; its random start and k-means seeding are not Faiss's
   (Faiss is not importable here), so trained matrices are not Faiss's either.
+* ``PCAMatrix.train`` takes the mean and the centred scatter matrix of the training rows on
+  the GPU (``ivfpq_pca_moments_device``, csrc/pca_moments.hip: fp64 column sums, the scatter
+  on the fp32 matrix cores in a fixed order) and the d x d eigendecomposition on the host in
+  float64.  Faiss leaves its scatter's summation order to ssyrk, so trained
+  matrices agree with Faiss's to rounding, not bit for bit.
 """
 from __future__ import annotations
 
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -41,21 +47,25 @@ def downcast_VectorTransform(vt):
 
 
 def write_VectorTransform(vt, path):
-    """faiss.write_VectorTransform (bench_gpu_1bn.py:507): one "LTra" record."""
+    """faiss.write_VectorTransform (bench_gpu_1bn.py:507): one "LTra" record, or "PcAm" for
+    a PCAMatrix."""
     if not vt.is_trained:
         raise RuntimeError("write_VectorTransform: transform is not trained")
     with open(path, "wb") as f:
-        f.write(faiss_io.serialize_linear(vt.A, vt.b, vt.d_in, vt.d_out, True))
+        f.write(_transform_bytes(vt))
 
 
 def read_VectorTransform(path):
-    """faiss.read_VectorTransform (bench_gpu_1bn.py:510) -> LinearTransform."""
+    """faiss.read_VectorTransform (bench_gpu_1bn.py:510) -> LinearTransform ("LTra") or
+    PCAMatrix ("PcAm")."""
     with open(path, "rb") as f:
         t = faiss_io.parse_vector_transform(f.read())
     return _linear_from_dict(t)
 
 
 def _linear_from_dict(t):
+    if t.get("kind") == "pca":
+        return _pca_from_dict(t)
     lt = LinearTransform(t["d_in"], t["d_out"], t["have_bias"])
     if t["is_trained"]:
         lt.set_matrix(t["A"], t["b"])
@@ -205,6 +215,186 @@ class OPQMatrix(LinearTransform):
         self.set_matrix(A.astype(np.float32))
 
 
+def pca_moments_device(x, stream=None):
+    """Column mean [d] and centred scatter matrix [d][d] (sum_r (x_r - mean)(x_r - mean)^T,
+    not divided by n) of a torch float32 CUDA tensor [n, d], as torch tensors on its device
+    (ivfpq_pca_moments_device: fp64 column sums, the scatter on the fp32 matrix cores)."""
+    import torch
+
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
+        raise RuntimeError("pca_moments_device: x must be a float32 CUDA tensor [n, d]")
+    x = x.contiguous()
+    n, d = x.shape
+    cur = torch.cuda.current_stream(x.device)
+    s = cur.cuda_stream if stream is None else int(stream)
+    with torch.cuda.device(x.device):
+        mean = torch.empty(d, dtype=torch.float32, device=x.device)
+        scatter = torch.empty((d, d), dtype=torch.float32, device=x.device)
+        if s != cur.cuda_stream:
+            # a caller's stream: x's producer and any pending use of the outputs' blocks are on
+            # the current stream; the call itself returns once `stream` has finished
+            cur.synchronize()
+        _lib.check(_lib.load().ivfpq_pca_moments_device(n, d, x.data_ptr(), mean.data_ptr(), scatter.data_ptr(),
+                                                        ctypes.c_void_p(s)))
+    return mean, scatter
+
+
+def pca_plan(n, d):
+    """How the scatter of n rows of d dimensions is split under the current chunk length
+    (ivfpq_pca_get_plan; host arithmetic): dict of chunks, chunk_rows, tiles."""
+    chunks, tiles, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _lib.check(_lib.load().ivfpq_pca_get_plan(int(n), int(d), ctypes.byref(chunks), ctypes.byref(rows),
+                                              ctypes.byref(tiles)))
+    return {"chunks": chunks.value, "chunk_rows": rows.value, "tiles": tiles.value}
+
+
+def pca_set_chunk_rows(rows):
+    """The scatter's row chunk (test hook ivfpq_pca_set_chunk_rows); 0 restores the default."""
+    _lib.check(_lib.load().ivfpq_pca_set_chunk_rows(int(rows)))
+
+
+class PCAMatrix(LinearTransform):
+    """Faiss PCAMatrix(d_in, d_out, eigen_power, random_rotation): y = A (x - mean), A the
+    first d_out principal directions, optionally whitened (eigen_power = -0.5) and followed by
+    a random rotation (beir faiss_search.py:359-413; bench_gpu_1bn.py:490-492 "PCAR<dout>,";
+    fairseq wav2vec/unsupervised/scripts/pca.py reads ``A`` and ``b`` back).
+
+    ``train`` computes the mean and the scatter matrix on the GPU (csrc/pca_moments.hip) and
+    the eigendecomposition on the host in float64 (numpy.linalg.eigh, Faiss's dsyev).  The
+    scatter is the centred sum and is not divided by n, so ``eigenvalues`` are those of the
+    scatter matrix.  Every n >= 1 takes this path (Faiss's Gram-matrix branch
+    for n < d_in is an optimisation).  The apply is LinearTransform's."""
+
+    def __init__(self, d_in=0, d_out=0, eigen_power=0.0, random_rotation=False):
+        super().__init__(d_in, d_out, True)
+        self.eigen_power = float(eigen_power)
+        self.random_rotation = bool(random_rotation)
+        self.balanced_bins = 0
+        self.max_points_per_d = 1000
+        self.seed = 1234
+        self.mean = np.zeros(0, np.float32)
+        self.eigenvalues = np.zeros(0, np.float32)
+        self.PCAMat = np.zeros(0, np.float32)
+
+    def _check_trainable(self):
+        if self.balanced_bins != 0:
+            raise RuntimeError("PCAMatrix: balanced_bins is not supported")
+        if self.d_in < 1:
+            raise RuntimeError("PCAMatrix: d_in must be at least 1")
+        if self.d_out > self.d_in:
+            raise RuntimeError(f"PCAMatrix: d_out = {self.d_out} > d_in = {self.d_in} (widening is not supported)")
+
+    def _subsample(self, n):
+        """The sorted rows train keeps of n (None: all), as OPQMatrix.train draws them."""
+        cap = self.max_points_per_d * self.d_in
+        if n <= cap:
+            return None
+        return np.sort(np.random.default_rng(self.seed).choice(n, cap, replace=False))
+
+    def train(self, x, device=None):
+        """x: numpy [n, d_in]; the kept rows are uploaded to GPU ``device`` for the moments."""
+        import torch
+
+        from .index import _default_device
+
+        self._check_trainable()
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, self.d_in)
+        if x.shape[0] < 1:
+            raise RuntimeError("PCAMatrix.train needs at least one training vector")
+        keep = self._subsample(x.shape[0])
+        if keep is not None:
+            x = x[keep]
+        device = _default_device() if device is None else int(device)
+        with warnings.catch_warnings():  # (a read-only array is only read: the tensor is copied to the device)
+            warnings.simplefilter("ignore", UserWarning)
+            xd = torch.from_numpy(x).to(f"cuda:{device}")
+        self._train_moments_device(xd, None)
+
+    def train_device(self, x, stream=None):
+        """train with the vectors already in HBM (torch float32 CUDA tensor [n, d_in])."""
+        import torch
+
+        self._check_trainable()
+        if x.dim() != 2 or x.shape[1] != self.d_in or x.dtype != torch.float32 or not x.is_cuda:
+            raise RuntimeError(f"train_device: x must be a float32 CUDA tensor [n, {self.d_in}]")
+        if x.shape[0] < 1:
+            raise RuntimeError("PCAMatrix.train needs at least one training vector")
+        keep = self._subsample(x.shape[0])
+        if keep is not None:
+            x = x.index_select(0, torch.from_numpy(keep).to(x.device))
+        self._train_moments_device(x, stream)
+
+    def _train_moments_device(self, x, stream):
+        mean, scatter = pca_moments_device(x, stream)
+        self.train_from_moments(mean.cpu().numpy(), scatter.cpu().numpy())
+
+    def train_from_moments(self, mean, scatter):
+        """The host half of train: mean [d_in] and the symmetric scatter (or covariance) matrix
+        [d_in][d_in] -> eigenvalues (descending), PCAMat (rows = eigenvectors), A and b."""
+        self._check_trainable()
+        d = self.d_in
+        mean = np.ascontiguousarray(mean, np.float32).reshape(-1)
+        S = np.asarray(scatter, np.float64)
+        if mean.size != d or S.shape != (d, d):
+            raise RuntimeError(f"train_from_moments: mean must be [{d}] and scatter [{d}][{d}]")
+        w, v = np.linalg.eigh(S)  # ascending, columns are eigenvectors
+        self.mean = mean
+        self.eigenvalues = np.ascontiguousarray(w[::-1], np.float32)
+        self.PCAMat = np.ascontiguousarray(v[:, ::-1].T, np.float32)
+        self.prepare_Ab()
+
+    def prepare_Ab(self):
+        """A and b from mean / eigenvalues / PCAMat (Faiss PCAMatrix::prepare_Ab without
+        balanced_bins): the first d_out eigenvectors, each scaled by eigenvalue ** eigen_power,
+        then the seeded random rotation; b = -A mean."""
+        self._check_trainable()
+        d, do = self.d_in, self.d_out
+        if self.mean.size != d or self.eigenvalues.size != d or self.PCAMat.size != d * d:
+            raise RuntimeError("prepare_Ab: mean / eigenvalues / PCAMat are not set")
+        A = self.PCAMat.reshape(d, d)[:do].astype(np.float64)
+        if self.eigen_power != 0:
+            ev = self.eigenvalues[:do].astype(np.float64)
+            if self.eigen_power < 0 and (ev <= 0).any():
+                i = int(np.argmax(ev <= 0))
+                raise RuntimeError(f"PCAMatrix: eigenvalue {i} is {ev[i]:g} <= 0, cannot be raised to the power "
+                                   f"{self.eigen_power:g} (lower d_out or eigen_power)")
+            A = A * (ev ** self.eigen_power)[:, None]
+        if self.random_rotation:
+            q, r = np.linalg.qr(np.random.default_rng(self.seed).standard_normal((do, do)))
+            A = (q * np.sign(np.diag(r))[None, :]).T @ A
+        A = A.astype(np.float32)
+        b = -(A.astype(np.float64) @ self.mean.astype(np.float64))
+        self.set_matrix(A, b.astype(np.float32))
+
+    def copy_from(self, other):
+        """Every field of ``other``; returns self (beir faiss_search.py:389 assigns it)."""
+        for name in ("d_in", "d_out", "have_bias", "is_trained", "eigen_power", "random_rotation", "balanced_bins",
+                     "max_points_per_d", "seed"):
+            setattr(self, name, getattr(other, name))
+        for name in ("A", "b", "mean", "eigenvalues", "PCAMat"):
+            v = getattr(other, name)
+            setattr(self, name, None if v is None else np.array(v, np.float32))
+        self._dev = {}
+        return self
+
+
+def _pca_from_dict(t):
+    p = PCAMatrix(t["d_in"], t["d_out"], t["eigen_power"], t["random_rotation"])
+    p.balanced_bins = t["balanced_bins"]
+    p.mean, p.eigenvalues, p.PCAMat = t["mean"], t["eigenvalues"], t["PCAMat"]
+    if t["is_trained"]:
+        p.set_matrix(t["A"], t["b"])
+    return p
+
+
+def _transform_bytes(vt):
+    """One VectorTransform record: "PcAm" for a PCAMatrix, "LTra" for the others."""
+    if isinstance(vt, PCAMatrix):
+        return faiss_io.serialize_pca(vt.eigen_power, vt.random_rotation, vt.balanced_bins, vt.mean, vt.eigenvalues,
+                                      vt.PCAMat, vt.A, vt.b, vt.d_in, vt.d_out, vt.is_trained)
+    return faiss_io.serialize_linear(vt.A, vt.b, vt.d_in, vt.d_out, vt.is_trained)
+
+
 class IndexPreTransform:
     """Faiss IndexPreTransform(chain, index): every vector is transformed on the GPU
     before the wrapped index sees it.  ``chain`` is a list of LinearTransform."""
@@ -254,7 +444,10 @@ class IndexPreTransform:
         x = np.ascontiguousarray(x, np.float32).reshape(-1, self.d)
         for t in self.chain:
             if not t.is_trained:
-                t.train(x)
+                if isinstance(t, PCAMatrix):  # its moments run on the wrapped index's GPU
+                    t.train(x, self.index.device)
+                else:
+                    t.train(x)
             x = t.apply(x, self.index.device)
         if not self.index.is_trained:
             self.index.train(x)

@@ -197,6 +197,29 @@ int ivfpq_merge_topk_device(int S, int64_t n, int k, int metric, const float* Di
 int ivfpq_linear_transform_device(int64_t n, int d_in, int d_out, const float* AT, const float* b, const float* x,
                                   float* y, void* stream);
 
+/* First and second moments of device rows, the GPU half of PCAMatrix::train (beir
+ * faiss_search.py:359-413; the "PCAR<dout>," front of bench_gpu_1bn.py:490-492): every
+ * pointer is device memory, x [n][d] fp32, mean_out [d], scatter_out [d][d].
+ * mean = the fp64 column sums over fixed row chunks, added in chunk order, divided by n and
+ * rounded to fp32 once.  scatter = sum_r (x_r - mean)(x_r - mean)^T, the centred sum (not
+ * Faiss's sum x x^T - n mean mean^T, which cancels in fp32), not divided by n, full and
+ * exactly symmetric: the subtraction in fp32, the products accumulated on the fp32 matrix
+ * cores per (tile, row chunk), the chunks' partial tiles added in chunk order.  No
+ * floating-point atomics: two runs on one input return the same bits.  Any d in
+ * [1, 65536]; n = 0 is an error, n = 1 gives a zero scatter.  The workspace is allocated
+ * inside; the call returns once the results are in place on `stream`. */
+int ivfpq_pca_moments_device(int64_t n, int d, const float* x, float* mean_out, float* scatter_out, void* stream);
+/* The row chunk of the scatter (process-wide; rounded up to 32 rows): rows > 0 sets it, 0
+ * (default) restores the length chosen from (n, d) alone.  The mean does not depend on it; the
+ * scatter's summation order does, so a caller who needs the same bits across processes leaves
+ * it alone.  The test suite uses it to reach the multi-chunk reduce with small n (declared
+ * here beside ivfpq_flat_index_set_range_rows, its model, not in include/ivfpq_test.h). */
+int ivfpq_pca_set_chunk_rows(int64_t rows);
+/* How ivfpq_pca_moments_device splits n rows of d dimensions under that setting: chunks of
+ * chunk_rows rows, tiles = the 64 x 64 upper-triangle output tiles.  Host arithmetic only.
+ * n < 1 or a shape the entry point rejects is an error.  Outputs are nullable. */
+int ivfpq_pca_get_plan(int64_t n, int d, int* chunks, int64_t* chunk_rows, int* tiles);
+
 /* Per-stage device timing (the nsys stage split of MICRO_GPU_profiling/classify_stages.py:113-181,
  * measured live with HIP events recorded on the launch stream around each stage).
  * get_timing waits for the recorded events, returns per-stage sums in ms and launch counts

@@ -313,6 +313,36 @@ def test_device_entry_points_on_a_side_stream(metric):
         ix.search_device(tx.double(), 10)
 
 
+# ------------------------------------------------- the segmented coarse quantizer
+@pytest.mark.parametrize("metric", METRICS)
+def test_segmented_coarse_quantizer_is_the_one_of_ivfpq(metric):
+    """nlist = 8192: the coarse quantizer takes its large-nlist path (no key matrix), which
+    IndexIVFFlat enters without IVF-PQ's planning arguments.  Self-consistency against an
+    IndexIVFPQ on the same centroids: the same top-1 assignment of the adds, and the same
+    probes in a search (the IVF-PQ coarse call is the one test_gpu_configs.py holds to the oracle)."""
+    import torch
+
+    d, nlist, nb, nq, nprobe, k, M = 16, 8192, 20000, 33, 8, 10, 8
+    xb, cent, xq = data(81, nb, d, metric), data(82, nlist, d, metric), data(83, nq, d, metric)
+    ids = np.random.default_rng(84).permutation(nb).astype(np.int64)
+    flat = build(xb, cent, metric, ids)
+    pq = faiss.IndexIVFPQ(None, d, nlist, M, 8, metric)
+    pq.set_trained(cent, data(85, M * 256, d // M, metric))
+    pq.add_with_ids(xb, ids)
+    assert flat.ntotal == pq.ntotal == nb
+    np.testing.assert_array_equal(flat.invlists.list_sizes(), pq.invlists.list_sizes())
+    flat.nprobe = pq.nprobe = nprobe
+    _, Iq = pq.coarse_device(torch.from_numpy(xq).cuda())
+    torch.cuda.synchronize()
+    Iq = Iq.cpu().numpy()
+    assert Iq.shape == (nq, nprobe) and (Iq >= 0).all() and (Iq < nlist).all()
+    D, I = flat.search(xq, k)
+    Dp, Ip = flat.search_preassigned(xq, k, Iq)
+    np.testing.assert_array_equal(I, Ip)
+    np.testing.assert_array_equal(D, Dp)
+    assert (I >= 0).any()  # (the probed lists are not all empty)
+
+
 # ------------------------------------------------------------- file round trip
 @pytest.mark.parametrize("metric", METRICS)
 def test_write_read_index_round_trip(metric, tmp_path):

@@ -57,6 +57,11 @@ struct IvfFlatArgs {
 // plan + scan + merge of one batch; the image holds fewer than 2^31 - 1 rows, 1 <= k <= 1024,
 // d % 4 == 0, nq * plan.S < 2^31
 void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& plan, hipStream_t s);
+// The planning alone, for every list-major scan (launch_ivfflat_search, ivf_sq.h): cnt zeroed,
+// tau set to "none", the buckets, item_off and used filled, the partial lists of unused slots
+// padded.  With plan.G pairs per item; a.x, a.vecs, a.ids and the outputs are not read.
+// probe_of (nullable): [nlist][nq], the probe column of every bucket entry.
+void launch_ivfflat_planning(const IvfFlatArgs& a, const IvfFlatPlan& plan, int32_t* probe_of, hipStream_t s);
 
 // D[i] = FLT_MAX (-FLT_MAX for ip), I[i] = -1: the result of searching an empty index (every
 // float-distance index), and the pad of partial lists no work item writes

@@ -49,11 +49,11 @@ __device__ __forceinline__ int range_count(int64_t rows) {
 // One thread per query: its usable probes (list in range and non-empty, not a repeat
 // of an earlier probe of the row when dedup) appended to their lists' buckets with the
 // query's running slot number.  The order inside a bucket is the atomics' order; no
-// result depends on it.
+// result depends on it.  probe_of (nullable) receives the probe column of every entry.
 __global__ __launch_bounds__(256) void k_ivfflat_plan(const int64_t* __restrict__ probes, int64_t nq, int nprobe,
                                                       const int64_t* __restrict__ list_off, int nlist, int dedup,
                                                       int32_t* __restrict__ cnt, int2* __restrict__ bucket,
-                                                      int32_t* __restrict__ used) {
+                                                      int32_t* __restrict__ used, int32_t* __restrict__ probe_of) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (q >= nq) return;
   const int64_t* row = probes + q * nprobe;
@@ -70,6 +70,7 @@ __global__ __launch_bounds__(256) void k_ivfflat_plan(const int64_t* __restrict_
     }
     const int at = atomicAdd(&cnt[l], 1);  // < nq: a list holds at most one pair per query
     bucket[l * nq + at] = make_int2((int)q, slot);
+    if (probe_of) probe_of[l * nq + at] = p;
     slot += range_count(rows);
   }
   used[q] = slot;
@@ -303,15 +304,19 @@ void launch_fill_empty(float* D, int64_t* I, int64_t n, bool ip, hipStream_t s) 
   hipLaunchKernelGGL(k_fill_empty, dim3(nblocks(n, 256)), dim3(256), 0, s, D, I, n, ip ? -FLT_MAX : FLT_MAX);
 }
 
-void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& p, hipStream_t s) {
-  if (a.nq <= 0) return;
+void launch_ivfflat_planning(const IvfFlatArgs& a, const IvfFlatPlan& p, int32_t* probe_of, hipStream_t s) {
   (void)hipMemsetAsync(a.cnt, 0, sizeof(int32_t) * a.nlist, s);
   (void)hipMemsetAsync(a.tau, 0xff, sizeof(uint32_t) * a.nq, s);  // no bound yet
   hipLaunchKernelGGL(k_ivfflat_plan, dim3(nblocks(a.nq, 256)), dim3(256), 0, s, a.probes, a.nq, a.nprobe, a.list_off,
-                     a.nlist, a.dedup ? 1 : 0, a.cnt, a.bucket, a.used);
+                     a.nlist, a.dedup ? 1 : 0, a.cnt, a.bucket, a.used, probe_of);
   hipLaunchKernelGGL(k_ivfflat_items, dim3(1), dim3(256), 0, s, a.cnt, a.list_off, a.nlist, p.G, a.item_off);
   hipLaunchKernelGGL(k_ivfflat_pad, dim3(nblocks((int64_t)p.S * a.nq * a.k, 256)), dim3(256), 0, s, a.used, a.nq, a.k,
                      p.S, a.ip ? -FLT_MAX : FLT_MAX, a.partD, a.partI);
+}
+
+void launch_ivfflat_search(const IvfFlatArgs& a, const IvfFlatPlan& p, hipStream_t s) {
+  if (a.nq <= 0) return;
+  launch_ivfflat_planning(a, p, nullptr, s);
   if (a.ip)
     launch_scan_kind<K_IP>(a, p, s);
   else

@@ -18,6 +18,7 @@ struct ListImage {
 // rows, n of them.
 struct PendingSet {
   size_t row_bytes = 0;
+  size_t image_slack = 0;  // bytes the merged image's rows are allocated past their end (a scan's read slack)
   DevBuf lists, ids, rows;
   int64_t n = 0, cap = 0;
 
@@ -98,7 +99,7 @@ inline std::vector<int64_t> merge_pending(PendingSet& q, ListImage& img, int nli
   }
   const int64_t n_out = off[nlist];
   ListImage out;
-  out.rows.ensure(std::max<size_t>(16, q.row_bytes * n_out));
+  out.rows.ensure(std::max<size_t>(16, q.row_bytes * n_out + q.image_slack));
   out.ids.ensure(std::max<size_t>(16, sizeof(int64_t) * n_out));
   out.off.ensure(sizeof(int64_t) * (nlist + 1));
   ListMergeArgs m;

@@ -8,26 +8,10 @@
 
 #include "code_store.h"
 #include "ivfpq.h"
+#include "sq_params.h"
 #include "sq_scan.h"
 
 using namespace chivf;
-
-namespace {
-
-const char* sq_qtype_name(int qtype) {
-  switch (qtype) {
-    case IVFPQ_SQ_8BIT: return "QT_8bit";
-    case IVFPQ_SQ_4BIT: return "QT_4bit";
-    case IVFPQ_SQ_8BIT_UNIFORM: return "QT_8bit_uniform";
-    case IVFPQ_SQ_4BIT_UNIFORM: return "QT_4bit_uniform";
-    case IVFPQ_SQ_FP16: return "QT_fp16";
-    case IVFPQ_SQ_8BIT_DIRECT: return "QT_8bit_direct";
-    case IVFPQ_SQ_6BIT: return "QT_6bit";
-    default: return nullptr;
-  }
-}
-
-}  // namespace
 
 struct ivfpq_sq_index : CodeStore {
   int d = 0, qtype = IVFPQ_SQ_FP16, metric = IVFPQ_METRIC_L2;
@@ -40,24 +24,13 @@ struct ivfpq_sq_index : CodeStore {
   ivfpq_sq_index() : CodeStore("IndexScalarQuantizer") {}
   bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
   bool uniform() const { return qtype == IVFPQ_SQ_8BIT_UNIFORM; }
-  size_t nparams() const { return codec == SQ_CODEC_FP16 ? 0 : uniform() ? 2 : 2 * (size_t)d; }
+  size_t nparams() const { return sq_nparams(qtype, d); }
   int64_t host_rows(int64_t n) const { return CodeStore::host_rows(n, sizeof(float) * d); }
 
   // the 8-bit codec's device parameters: per dimension, a uniform pair repeated d times
   void upload_params() {
     quiesce();
-    if (codec == SQ_CODEC_8BIT) {
-      std::vector<float> mn(d), df(d);
-      for (int j = 0; j < d; j++) {
-        mn[j] = uniform() ? params[0] : params[j];
-        df[j] = uniform() ? params[1] : params[(size_t)d + j];
-      }
-      d_vmin.ensure(sizeof(float) * d);
-      d_vdiff.ensure(sizeof(float) * d);
-      HIPCHECK(hipMemcpyAsync(d_vmin.p, mn.data(), sizeof(float) * d, hipMemcpyHostToDevice, stream));
-      HIPCHECK(hipMemcpyAsync(d_vdiff.p, df.data(), sizeof(float) * d, hipMemcpyHostToDevice, stream));
-      HIPCHECK(hipStreamSynchronize(stream));
-    }
+    if (codec == SQ_CODEC_8BIT) sq_upload_params(params, qtype, d, d_vmin, d_vdiff, stream);
     trained = true;
   }
 
@@ -81,22 +54,7 @@ struct ivfpq_sq_index : CodeStore {
     std::vector<uint32_t> bits(2 * (size_t)d);
     HIPCHECK(hipMemcpyAsync(bits.data(), w_mm.p, sizeof(uint32_t) * 2 * d, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
-    std::vector<float> mn(d), mx(d);
-    for (int j = 0; j < d; j++) {
-      mn[j] = sq_minmax_value(bits[j]);
-      mx[j] = sq_minmax_value(bits[(size_t)d + j]);
-    }
-    if (uniform()) {
-      const float lo_all = *std::min_element(mn.begin(), mn.end());
-      const float hi_all = *std::max_element(mx.begin(), mx.end());
-      params = {lo_all, hi_all - lo_all};
-    } else {
-      params.resize(2 * (size_t)d);
-      for (int j = 0; j < d; j++) {
-        params[j] = mn[j];
-        params[(size_t)d + j] = mx[j] - mn[j];
-      }
-    }
+    params = sq_trained_from_minmax(bits, qtype, d);
     upload_params();
   }
 
@@ -210,15 +168,12 @@ int ivfpq_sq_create(int d, int qtype, int metric, int device, ivfpq_sq_index** o
     require(out != nullptr, "null output pointer");
     require(d >= 4 && d <= 2048 && d % 4 == 0,
             "IndexScalarQuantizer: d must be a multiple of 4 in [4, 2048] (d = " + std::to_string(d) + ")");
-    const char* qn = sq_qtype_name(qtype);
-    require(qn != nullptr, "unknown scalar quantizer type " + std::to_string(qtype));
-    require(qtype == IVFPQ_SQ_8BIT || qtype == IVFPQ_SQ_8BIT_UNIFORM || qtype == IVFPQ_SQ_FP16,
-            std::string("scalar quantizer type ") + qn + " is not supported (QT_fp16, QT_8bit, QT_8bit_uniform)");
+    check_sq_qtype(qtype);
     require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
     auto h = std::make_unique<ivfpq_sq_index>();
     h->d = d;
     h->qtype = qtype;
-    h->codec = qtype == IVFPQ_SQ_FP16 ? SQ_CODEC_FP16 : SQ_CODEC_8BIT;
+    h->codec = sq_codec_of(qtype);
     h->code_size = sq_code_size(h->codec, d);
     h->row_bytes = (size_t)h->code_size;
     h->slack = kSqScanSlack;  // the scan's 16-byte loads may straddle the last row's end

@@ -16,6 +16,7 @@ from .index import (  # noqa: F401
     IndexFlatL2,
     IndexIVFFlat,
     IndexIVFPQ,
+    IndexIVFScalarQuantizer,
     IndexPQ,
     IndexScalarQuantizer,
     ParameterSpace,

@@ -166,6 +166,34 @@ SIGNATURES = {
     "ivfpq_sq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
     "ivfpq_sq_encode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_u8p]),
     "ivfpq_sq_decode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, c_f32p]),
+    # IVF over scalar-quantizer codes (IndexIVFScalarQuantizer)
+    "ivfpq_ivfsq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.POINTER(c_handle)]),
+    "ivfpq_ivfsq_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfsq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
+    "ivfpq_ivfsq_set_trained": (ctypes.c_int, [c_handle, c_f32p, c_f32p, ctypes.c_int64]),
+    "ivfpq_ivfsq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_i64p]),
+    "ivfpq_ivfsq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "ivfpq_ivfsq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_i64p, c_u8p, c_i64p]),
+    "ivfpq_ivfsq_reset": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfsq_set_nprobe": (ctypes.c_int, [c_handle, ctypes.c_int]),
+    "ivfpq_ivfsq_get_nprobe": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfsq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_ivfsq_search_preassigned": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_i64p,
+                                                      c_f32p, c_f32p, c_i64p]),
+    "ivfpq_ivfsq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_ivfsq_search_preassigned_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p,
+                                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ivfpq_ivfsq_ntotal": (ctypes.c_int64, [c_handle]),
+    "ivfpq_ivfsq_is_trained": (ctypes.c_int, [c_handle]),
+    "ivfpq_ivfsq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 6),
+    "ivfpq_ivfsq_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_ivfsq_get_trained": (ctypes.c_int, [c_handle, c_f32p, c_i64p]),
+    "ivfpq_ivfsq_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
+    "ivfpq_ivfsq_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_u8p, c_i64p]),
     # flat binary codes (IndexBinaryFlat)
     "ivfpq_bin_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_handle)]),
     "ivfpq_bin_free": (ctypes.c_int, [c_handle]),

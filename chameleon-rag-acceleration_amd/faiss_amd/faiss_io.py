@@ -47,6 +47,13 @@ The layout is restated from upstream Faiss 1.7.1 ``impl/index_write.cpp`` /
       (no by_residual / code_size / PQ block)
     Unpinned like the others: no Faiss-written "IwFl" file exists on the build machine.
 
+    "IwSq"                                   IndexIVFScalarQuantizer ("IVF<nlist>,SQ8" / ",SQfp16" keys)
+      the IVF header of "IwPQ": index header, nlist u64, nprobe u64, quantizer, direct map
+      SQ block of "IxSQ" below (qtype, rangestat, rangestat_arg, d, code_size, trained)
+      code_size u64, by_residual u8
+      "ilar" as above with that code size
+    Unpinned like the others: no Faiss-written "IwSq" file exists on the build machine.
+
     "IxSQ"                                   IndexScalarQuantizer (beir faiss_search.py:415-459)
       index header
       SQ:          qtype i32, rangestat i32 (0 = RS_minmax), rangestat_arg f32 (0), d u64, code_size u64,
@@ -86,6 +93,7 @@ FOURCC_IVFPQ = b"IwPQ"
 FOURCC_PQ = b"IxPq"
 FOURCC_IVFFLAT = b"IwFl"
 FOURCC_SQ = b"IxSQ"
+FOURCC_IVFSQ = b"IwSq"
 SQ_QT_8BIT, SQ_QT_8BIT_UNIFORM, SQ_QT_FP16 = 0, 2, 4  # the scalar quantizer types that are read and written
 FOURCC_BINARY_FLAT = b"IBxF"
 FOURCC_FLAT = {0: b"IxFI", 1: b"IxF2"}  # metric_type: 0 = INNER_PRODUCT, 1 = L2
@@ -99,7 +107,7 @@ FOURCC_PCA = b"PcAm"
 
 def is_faiss_file(path) -> bool:
     with open(path, "rb") as f:
-        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT, FOURCC_SQ,
+        return f.read(4) in (FOURCC_IVFPQ, b"IvPQ", FOURCC_PRETRANSFORM, FOURCC_PQ, FOURCC_IVFFLAT, FOURCC_SQ, FOURCC_IVFSQ,
                              FOURCC_FLAT[0], FOURCC_FLAT[1])
 
 
@@ -154,6 +162,7 @@ def parse_index(buf: bytes) -> dict:
     "pretransform", d, ntotal, metric, chain: [{A [d_out][d_in], b, have_bias,
     d_in, d_out, is_trained}], index: the IVF-PQ dict}; IndexPQ -> kind "pq";
     IndexIVFFlat -> kind "ivfflat" (_parse_ivfflat); IndexScalarQuantizer -> kind "sq" (_parse_sq);
+    IndexIVFScalarQuantizer -> kind "ivfsq" (_parse_ivfsq);
     a top-level IndexFlatL2 / IndexFlatIP -> kind "flat" (_parse_flat)."""
     r = _Reader(buf)
     h = r.fourcc()
@@ -183,6 +192,8 @@ def _parse_sub(r: "_Reader", h: bytes) -> dict:
         return _parse_ivfflat(r)
     if h == FOURCC_SQ:
         return _parse_sq(r)
+    if h == FOURCC_IVFSQ:
+        return _parse_ivfsq(r)
     return _parse_pq(r) if h == FOURCC_PQ else _parse_ivfpq(r, h)
 
 
@@ -268,22 +279,39 @@ def sq_shape(qtype, d):
     raise RuntimeError(f"unsupported scalar quantizer type {qtype} (QT_fp16, QT_8bit, QT_8bit_uniform)")
 
 
-def _parse_sq(r: "_Reader") -> dict:
-    """IndexScalarQuantizer after its fourcc -> {kind "sq", d, ntotal, qtype, metric, is_trained,
-    code_size, trained f32[...], codes u8 [ntotal][code_size]}."""
-    d, ntotal, is_trained, metric = r.header()
+def _parse_sq_block(r: "_Reader"):
+    """The ScalarQuantizer record -> (qtype, d, code_size, trained, rangestat)."""
     qtype = r.fmt("i")
     rangestat = r.fmt("i")
     r.fmt("f")  # rangestat_arg
     sd = r.fmt("Q")
     code_size = r.fmt("Q")
-    trained = r.vector(np.float32)
-    codes = r.vector(np.uint8)
+    return qtype, sd, code_size, r.vector(np.float32), rangestat
+
+
+def _check_sq_block(qtype, d, sd, code_size, trained, rangestat, is_trained):
+    """The record against the index that holds it (checked once the index is read to its end,
+    so that a truncated file is reported as truncated); returns the code size."""
     cs, nt = sq_shape(qtype, d)
     if rangestat != 0:
         raise RuntimeError("only the RS_minmax range statistic is supported")
     if sd != d or code_size != cs or (is_trained and trained.size != nt):
         raise RuntimeError("scalar quantizer shape does not match the index")
+    return cs
+
+
+def _sq_block(d, qtype, trained) -> bytes:
+    cs, _ = sq_shape(qtype, d)
+    return struct.pack("<iifQQ", qtype, 0, 0.0, d, cs) + _vector(np.ascontiguousarray(trained, np.float32).reshape(-1))
+
+
+def _parse_sq(r: "_Reader") -> dict:
+    """IndexScalarQuantizer after its fourcc -> {kind "sq", d, ntotal, qtype, metric, is_trained,
+    code_size, trained f32[...], codes u8 [ntotal][code_size]}."""
+    d, ntotal, is_trained, metric = r.header()
+    qtype, sd, code_size, trained, rangestat = _parse_sq_block(r)
+    codes = r.vector(np.uint8)
+    cs = _check_sq_block(qtype, d, sd, code_size, trained, rangestat, is_trained)
     if codes.size != ntotal * cs:
         raise RuntimeError("IndexScalarQuantizer codes do not match ntotal")
     return {"kind": "sq", "d": d, "ntotal": ntotal, "qtype": qtype, "metric": metric, "is_trained": is_trained,
@@ -295,9 +323,8 @@ def serialize_sq(d, qtype, metric, trained, codes, is_trained=True) -> bytes:
     Unpinned against Faiss, like the other layouts (see the module docstring)."""
     cs, _ = sq_shape(qtype, d)
     codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
-    return b"".join([FOURCC_SQ, _header(d, codes.size // cs, is_trained, metric),
-                     struct.pack("<iifQQ", qtype, 0, 0.0, d, cs),
-                     _vector(np.ascontiguousarray(trained, np.float32).reshape(-1)), _vector(codes)])
+    return b"".join([FOURCC_SQ, _header(d, codes.size // cs, is_trained, metric), _sq_block(d, qtype, trained),
+                     _vector(codes)])
 
 
 def parse_index_binary(buf: bytes) -> dict:
@@ -492,6 +519,32 @@ def _parse_ivfflat(r: _Reader) -> dict:
     lists = [(ids, codes.view(np.float32).reshape(len(ids), d)) for ids, codes in _parse_ilar(r, nlist, 4 * d, ntotal)]
     return {"kind": "ivfflat", "d": d, "nlist": nlist, "nprobe": nprobe, "metric": metric, "is_trained": is_trained,
             "centroids": xb.reshape(nlist, d) if xb.size else xb, "lists": lists}
+
+
+def _parse_ivfsq(r: _Reader) -> dict:
+    """IndexIVFScalarQuantizer after its fourcc -> {kind "ivfsq", d, nlist, nprobe, qtype, metric,
+    by_residual, is_trained, code_size, centroids [nlist][d], trained f32[...],
+    lists: [(ids i64[n], codes u8[n][code_size])]}."""
+    d, ntotal, is_trained, metric, nlist, nprobe, xb = _parse_ivf_header(r)
+    qtype, sd, sq_cs, trained, rangestat = _parse_sq_block(r)
+    code_size = r.fmt("Q")
+    by_residual = r.fmt("B") != 0
+    cs = _check_sq_block(qtype, d, sd, sq_cs, trained, rangestat, is_trained)
+    if code_size != cs:
+        raise RuntimeError("IndexIVFScalarQuantizer code size does not match its quantizer")
+    lists = _parse_ilar(r, nlist, cs, ntotal)
+    return {"kind": "ivfsq", "d": d, "nlist": nlist, "nprobe": nprobe, "qtype": qtype, "metric": metric,
+            "by_residual": by_residual, "is_trained": is_trained, "code_size": cs,
+            "centroids": xb.reshape(nlist, d) if xb.size else xb, "trained": trained, "lists": lists}
+
+
+def serialize_ivfsq(d, nlist, nprobe, qtype, metric, by_residual, centroids, trained, lists, is_trained=True) -> bytes:
+    """The inverse of parse_index for kind "ivfsq": lists = [(ids i64[n], codes u8[n][code_size])].
+    Unpinned against Faiss, like the other layouts (see the module docstring)."""
+    cs, _ = sq_shape(qtype, d)
+    out = _ivf_header(FOURCC_IVFSQ, d, nlist, nprobe, metric, centroids, lists, is_trained)
+    out += [_sq_block(d, qtype, trained), struct.pack("<QB", cs, 1 if by_residual else 0)]
+    return b"".join(out + _ilar(nlist, cs, lists))
 
 
 def _header(d, ntotal, is_trained, metric):

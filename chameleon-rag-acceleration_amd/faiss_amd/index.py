@@ -967,7 +967,7 @@ class _FlatInvertedLists:
 
     def list_sizes(self):
         out = np.empty(self._o.nlist, np.int64)
-        _lib.check(_lib.load().ivfpq_ivfflat_get_list_sizes(self._o._h, _ptr(out, _lib.c_i64p)))
+        _lib.check(self._o._fn("get_list_sizes")(self._o._h, _ptr(out, _lib.c_i64p)))
         return out
 
     def list_size(self, l):
@@ -977,8 +977,8 @@ class _FlatInvertedLists:
         n = self.list_size(l)
         vecs = np.empty((n, self._o.d), np.float32)
         ids = np.empty(n, np.int64)
-        _lib.check(_lib.load().ivfpq_ivfflat_get_list(self._o._h, int(l), _ptr(vecs, _lib.c_f32p),
-                                                      _ptr(ids, _lib.c_i64p)))
+        _lib.check(self._o._fn("get_list")(self._o._h, int(l), _ptr(vecs, _lib.c_f32p),
+                                           _ptr(ids, _lib.c_i64p)))
         return vecs, ids
 
     def get_vectors(self, l):
@@ -1000,6 +1000,11 @@ class IndexIVFFlat:
     ground truth of ``compute_ground_truth.py:311``).  The coarse quantizer is the
     IndexIVFPQ one; the lists live in HBM only."""
 
+    _prefix = "ivfpq_ivfflat_"  # the C-ABI family of the handle (IndexIVFScalarQuantizer has its own)
+
+    def _fn(self, name):
+        return getattr(_lib.load(), self._prefix + name)
+
     def __init__(self, quantizer, d, nlist, metric=METRIC_L2, device=None):
         self.d = int(d)
         self.nlist = int(nlist)
@@ -1013,31 +1018,31 @@ class IndexIVFFlat:
         self.niter_coarse = 25
         self.seed = 1234
         h = _lib.c_handle()
-        _lib.check(_lib.load().ivfpq_ivfflat_create(self.d, self.nlist, metric, self.device, ctypes.byref(h)))
+        _lib.check(self._fn("create")(self.d, self.nlist, metric, self.device, ctypes.byref(h)))
         self._h = h
         self.invlists = _FlatInvertedLists(self)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_ivfflat_free(h)
+            getattr(_lib._lib, self._prefix + "free")(h)
             self._h = None
 
     @property
     def ntotal(self):
-        return int(_lib.load().ivfpq_ivfflat_ntotal(self._h))
+        return int(self._fn("ntotal")(self._h))
 
     @property
     def is_trained(self):
-        return bool(_lib.load().ivfpq_ivfflat_is_trained(self._h))
+        return bool(self._fn("is_trained")(self._h))
 
     @property
     def nprobe(self):
-        return int(_lib.load().ivfpq_ivfflat_get_nprobe(self._h))
+        return int(self._fn("get_nprobe")(self._h))
 
     @nprobe.setter
     def nprobe(self, p):
-        _lib.check(_lib.load().ivfpq_ivfflat_set_nprobe(self._h, int(p)))
+        _lib.check(self._fn("set_nprobe")(self._h, int(p)))
 
     @property
     def code_size(self):
@@ -1045,7 +1050,7 @@ class IndexIVFFlat:
 
     def centroids(self):
         c = np.empty((self.nlist, self.d), np.float32)
-        _lib.check(_lib.load().ivfpq_ivfflat_get_centroids(self._h, _ptr(c, _lib.c_f32p)))
+        _lib.check(self._fn("get_centroids")(self._h, _ptr(c, _lib.c_f32p)))
         return c
 
     _sync_quantizer = IndexIVFPQ._sync_quantizer
@@ -1053,29 +1058,29 @@ class IndexIVFFlat:
     # ----------------------------------------------------------- build path
     def train(self, x):
         x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_ivfflat_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_coarse,
-                                                   self.seed))
+        _lib.check(self._fn("train")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_coarse,
+                                     self.seed))
         self._sync_quantizer()
 
     def set_trained(self, centroids):
         """Install trained coarse centroids [nlist][d]."""
         c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
-        _lib.check(_lib.load().ivfpq_ivfflat_set_trained(self._h, _ptr(c, _lib.c_f32p)))
+        _lib.check(self._fn("set_trained")(self._h, _ptr(c, _lib.c_f32p)))
         self._sync_quantizer()
 
     def add(self, x):
         x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_ivfflat_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), None))
+        _lib.check(self._fn("add")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), None))
 
     def add_with_ids(self, x, ids):
         x = _f32(x, self.d)
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
         if ids.shape[0] != x.shape[0]:
             raise RuntimeError("ids and x have different lengths")
-        _lib.check(_lib.load().ivfpq_ivfflat_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(ids, _lib.c_i64p)))
+        _lib.check(self._fn("add")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(ids, _lib.c_i64p)))
 
     def reset(self):
-        _lib.check(_lib.load().ivfpq_ivfflat_reset(self._h))
+        _lib.check(self._fn("reset")(self._h))
 
     # ------------------------------------------------------------ search path
     _check_k = IndexIVFPQ._check_k
@@ -1090,8 +1095,8 @@ class IndexIVFFlat:
         n = x.shape[0]
         D = np.empty((n, k), np.float32)
         I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_ivfflat_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                                    _ptr(I, _lib.c_i64p)))
+        _lib.check(self._fn("search")(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
+                                      _ptr(I, _lib.c_i64p)))
         return D, I
 
     def _search_preassigned(self, x, k, Iq, Dq=None):
@@ -1108,9 +1113,9 @@ class IndexIVFFlat:
             Dqp = _ptr(Dq, _lib.c_f32p)
         D = np.empty((n, k), np.float32)
         I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_ivfflat_search_preassigned(self._h, n, _ptr(x, _lib.c_f32p), int(k),
-                                                                _ptr(Iq, _lib.c_i64p), Dqp, _ptr(D, _lib.c_f32p),
-                                                                _ptr(I, _lib.c_i64p)))
+        _lib.check(self._fn("search_preassigned")(self._h, n, _ptr(x, _lib.c_f32p), int(k),
+                                                  _ptr(Iq, _lib.c_i64p), Dqp, _ptr(D, _lib.c_f32p),
+                                                  _ptr(I, _lib.c_i64p)))
         return D, I
 
     # ------------------------------------------------- device (torch) entry points
@@ -1122,8 +1127,8 @@ class IndexIVFFlat:
         self._check_k(k)
         self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
         D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(_lib.load().ivfpq_ivfflat_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                                           I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
+        _lib.check(self._fn("search_device")(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
+                                             I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
         return D, I
 
     def search_preassigned_device(self, x, k, Iq, Dq=None, D=None, I=None, stream=None):
@@ -1137,7 +1142,7 @@ class IndexIVFFlat:
         if Dq is not None:
             self._check_dev(Dq, "Dq", torch.float32, (n, self.nprobe))
         D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(_lib.load().ivfpq_ivfflat_search_preassigned_device(
+        _lib.check(self._fn("search_preassigned_device")(
             self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
             D.data_ptr(), I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
         return D, I
@@ -1152,9 +1157,9 @@ class IndexIVFFlat:
         self._check_dev(x, "x", torch.float32, (n, self.d))
         if ids is not None:
             self._check_dev(ids, "ids", torch.int64, (n,))
-        _lib.check(_lib.load().ivfpq_ivfflat_add_device(self._h, n, x.data_ptr(),
-                                                        ids.data_ptr() if ids is not None else None,
-                                                        ctypes.c_void_p(self._stream(x, stream))))
+        _lib.check(self._fn("add_device")(self._h, n, x.data_ptr(),
+                                          ids.data_ptr() if ids is not None else None,
+                                          ctypes.c_void_p(self._stream(x, stream))))
 
 
 class ScalarQuantizer:
@@ -1330,6 +1335,107 @@ class IndexScalarQuantizer:
                                                    ctypes.c_void_p(self._stream(x, stream))))
 
 
+class _CodeInvertedLists:
+    """index.invlists of an IndexIVFScalarQuantizer (faiss ArrayInvertedLists read API): the
+    codes of a list are its rows' scalar-quantizer codes, ``code_size`` bytes each."""
+
+    def __init__(self, owner):
+        self._o = owner
+
+    nlist = _FlatInvertedLists.nlist
+    list_sizes = _FlatInvertedLists.list_sizes
+    list_size = _FlatInvertedLists.list_size
+    get_ids = _FlatInvertedLists.get_ids
+    imbalance_factor = _InvertedLists.imbalance_factor
+
+    @property
+    def code_size(self):
+        return self._o.code_size
+
+    def _get(self, l):
+        n = self.list_size(l)
+        codes = np.empty((n, self._o.code_size), np.uint8)
+        ids = np.empty(n, np.int64)
+        _lib.check(self._o._fn("get_list")(self._o._h, int(l), _ptr(codes, _lib.c_u8p), _ptr(ids, _lib.c_i64p)))
+        return codes, ids
+
+    def get_codes(self, l):
+        return self._get(l)[0].reshape(-1)
+
+
+class IndexIVFScalarQuantizer(IndexIVFFlat):
+    """faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric, by_residual) for QT_fp16,
+    QT_8bit and QT_8bit_uniform (the ``IVF<nlist>,SQ8`` / ``IVF<nlist>,SQfp16`` factory keys): an
+    IndexIVFFlat whose lists hold IndexScalarQuantizer's codes, of the vector or (``by_residual``,
+    the default) of the vector minus its list's centroid, decoded inside the scan.  With QT_fp16
+    and ``by_residual=False`` it is what ``co.useFloat16 = True`` makes of an ``IVF..,Flat`` key in
+    ``bench_gpu_1bn.py``.  Every method of IndexIVFFlat; ``search_preassigned`` reads ``Dq`` for the
+    inner product with ``by_residual`` (None: zeros) and ignores it otherwise."""
+
+    _prefix = "ivfpq_ivfsq_"
+
+    def __init__(self, quantizer, d, nlist, qtype, metric=METRIC_L2, by_residual=True, device=None):
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.qtype = int(qtype)
+        self.metric_type = metric
+        self.by_residual = bool(by_residual)
+        self.device = _default_device() if device is None else int(device)
+        if quantizer is None:
+            quantizer = (IndexFlatIP if metric == METRIC_INNER_PRODUCT else IndexFlatL2)(d, self.device)
+        self.quantizer = quantizer
+        self.parallel_mode = 0
+        self.verbose = False
+        self.niter_coarse = 25
+        self.seed = 1234
+        h = _lib.c_handle()
+        _lib.check(self._fn("create")(self.d, self.nlist, self.qtype, metric, int(self.by_residual), self.device,
+                                      ctypes.byref(h)))
+        self._h = h
+        cs = ctypes.c_int()
+        _lib.check(self._fn("get_dims")(h, None, None, None, None, None, ctypes.byref(cs)))
+        self._code_size = cs.value
+        self.sq = ScalarQuantizer(self)
+        self.invlists = _CodeInvertedLists(self)
+
+    @property
+    def code_size(self):
+        return self._code_size
+
+    def _trained(self):
+        if not self.is_trained:
+            return np.zeros(0, np.float32)
+        n = ctypes.c_int64()
+        _lib.check(self._fn("get_trained")(self._h, None, ctypes.byref(n)))
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            _lib.check(self._fn("get_trained")(self._h, _ptr(out, _lib.c_f32p), None))
+        return out
+
+    def set_trained(self, centroids, sq_trained=()):
+        """Install trained coarse centroids [nlist][d] and ``sq.trained`` (see ScalarQuantizer.trained)."""
+        c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
+        t = np.ascontiguousarray(sq_trained, np.float32).reshape(-1)
+        _lib.check(self._fn("set_trained")(self._h, _ptr(c, _lib.c_f32p), _ptr(t, _lib.c_f32p), t.size))
+        self._sync_quantizer()
+
+    def add_codes(self, list_no, codes, ids=None):
+        """Append precomputed codes uint8 [n][code_size] to the lists ``list_no`` [n] with labels
+        ``ids`` (None: sequential), as read from an index file."""
+        list_no = np.ascontiguousarray(list_no, np.int64).reshape(-1)
+        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.code_size)
+        n = list_no.shape[0]
+        if codes.shape[0] != n:
+            raise RuntimeError("codes and list_no have different lengths")
+        idp = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            if ids.shape[0] != n:
+                raise RuntimeError("ids and list_no have different lengths")
+            idp = _ptr(ids, _lib.c_i64p)
+        _lib.check(self._fn("add_codes")(self._h, n, _ptr(list_no, _lib.c_i64p), _ptr(codes, _lib.c_u8p), idp))
+
+
 class IndexBinaryFlat:
     """faiss.IndexBinaryFlat(d): exact Hamming search over uint8 codes of ``d`` bits (beir
     faiss_search.py BinaryFaissSearch builds ``IndexBinaryFlat(dim * 8)``).  ``search`` returns
@@ -1479,6 +1585,7 @@ _FACTORY_RE = re.compile(r"^(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x(\d+))?
 _IVFFLAT_FACTORY_RE = re.compile(r"^IVF(\d+),Flat$")
 _SQ_FACTORY_RE = re.compile(r"^SQ(\w+)$")
 _SQ_FACTORY_TYPES = {"8": ScalarQuantizer.QT_8bit, "fp16": ScalarQuantizer.QT_fp16}
+_IVFSQ_FACTORY_RE = re.compile(r"^IVF(\d+),SQ(\w+)$")
 _PCA_FRONT_RE = re.compile(r"^PCA(W?)(R?)(\d+),(.+)$")
 
 
@@ -1489,7 +1596,7 @@ def parse_factory(key):
     if not m:
         raise RuntimeError(f"index_factory: unsupported key {key!r} "
                            "(supported: '[OPQ<M>[_<dout>],]IVF<nlist>,PQ<M>[x8]', '[OPQ<M>[_<dout>],]PQ<M>[x8]', "
-                           "'IVF<nlist>,Flat', 'SQ8', 'SQfp16', 'Flat', each also behind a 'PCA[W][R]<dout>,' front)")
+                           "'IVF<nlist>,Flat', 'IVF<nlist>,SQ8', 'IVF<nlist>,SQfp16', 'SQ8', 'SQfp16', 'Flat', each also behind a 'PCA[W][R]<dout>,' front)")
     nbits = int(m.group(5)) if m.group(5) else 8
     base = (int(m.group(3)), int(m.group(4)), nbits)
     if m.group(1) is None:
@@ -1540,6 +1647,18 @@ def parse_sq_factory(key):
     return _SQ_FACTORY_TYPES[m.group(1)]
 
 
+def parse_ivfsq_factory(key):
+    """'IVF<nlist>,SQ8' / 'IVF<nlist>,SQfp16' -> (nlist, quantizer type); None for any other key;
+    'IVF<nlist>,SQ<x>' with another x (Faiss also has SQ4 and SQ6) raises, naming the key."""
+    m = _IVFSQ_FACTORY_RE.match(key.replace(" ", ""))
+    if not m:
+        return None
+    if m.group(2) not in _SQ_FACTORY_TYPES:
+        raise RuntimeError(f"index_factory: unsupported scalar quantizer key {key!r} "
+                           "(supported: 'IVF<nlist>,SQ8', 'IVF<nlist>,SQfp16')")
+    return int(m.group(1)), _SQ_FACTORY_TYPES[m.group(2)]
+
+
 def parse_binary_factory(key):
     """'BFlat' -> True; any other key raises, naming it (Faiss also has BIVF, BHNSW, BHash)."""
     if key.replace(" ", "") != "BFlat":
@@ -1558,7 +1677,8 @@ def index_factory(d, key, metric=METRIC_L2, device=None):
     OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), the flat
     "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
     "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
-    truth of compute_ground_truth.py:311), the flat scalar quantizers "SQ8" / "SQfp16", and
+    truth of compute_ground_truth.py:311), "IVF<nlist>,SQ8" / "IVF<nlist>,SQfp16" (an
+    IndexIVFScalarQuantizer, by_residual as in Faiss), the flat scalar quantizers "SQ8" / "SQfp16", and
     "Flat" (an IndexFlat of the given metric: beir faiss_search.py:337).  Each may stand behind
     a PCA front, "PCA<dout>," / "PCAR<dout>," / "PCAW<dout>," / "PCAWR<dout>," (bench_gpu_1bn.py:
     490-492): IndexPreTransform(PCAMatrix(d, dout, ...), the rest built at dout)."""
@@ -1581,6 +1701,9 @@ def index_factory(d, key, metric=METRIC_L2, device=None):
     nlist = parse_ivfflat_factory(key)
     if nlist is not None:
         return IndexIVFFlat(None, d, nlist, metric, device)
+    f = parse_ivfsq_factory(key)
+    if f is not None:
+        return IndexIVFScalarQuantizer(None, d, f[0], f[1], metric, True, device)
     f = parse_pq_factory(key)
     if f is not None:
         if len(f) == 2:
@@ -1644,6 +1767,15 @@ def _sq_bytes(index):
                                  index._codes(0, index.ntotal))
 
 
+def _ivfsq_bytes(index):
+    if not index.is_trained:
+        raise RuntimeError("IndexIVFScalarQuantizer is written once trained")
+    inv = index.invlists
+    lists = [inv._get(l)[::-1] for l in range(index.nlist)]
+    return faiss_io.serialize_ivfsq(index.d, index.nlist, index.nprobe, index.qtype, index.metric_type,
+                                    index.by_residual, index.centroids(), index.sq.trained, lists)
+
+
 def _flat_bytes(index):
     return faiss_io.serialize_flat(index.d, index.metric_type, index.xb.reshape(-1, index.d))
 
@@ -1651,6 +1783,8 @@ def _flat_bytes(index):
 def _sub_bytes(index):
     if isinstance(index, IndexFlat):
         return _flat_bytes(index)
+    if isinstance(index, IndexIVFScalarQuantizer):
+        return _ivfsq_bytes(index)
     if isinstance(index, IndexIVFFlat):
         return _ivfflat_bytes(index)
     if isinstance(index, IndexScalarQuantizer):
@@ -1660,7 +1794,7 @@ def _sub_bytes(index):
 
 def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
-    IndexIVFFlat / IndexScalarQuantizer / IndexFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
+    IndexIVFFlat / IndexIVFScalarQuantizer / IndexScalarQuantizer / IndexFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform, _transform_bytes
 
@@ -1682,6 +1816,10 @@ def write_index(index, path, fmt="faiss"):
         if fmt != "faiss":
             raise RuntimeError("IndexScalarQuantizer is written in the Faiss layout")
         buf = _sq_bytes(index)
+    elif isinstance(index, IndexIVFScalarQuantizer):
+        if fmt != "faiss":
+            raise RuntimeError("IndexIVFScalarQuantizer is written in the Faiss layout")
+        buf = _ivfsq_bytes(index)
     elif isinstance(index, IndexIVFFlat):
         if fmt != "faiss":
             raise RuntimeError("IndexIVFFlat is written in the Faiss layout")
@@ -1732,6 +1870,21 @@ def _ivfflat_from_dict(z, device):
     return idx
 
 
+def _ivfsq_from_dict(z, device):
+    """Centroids, quantizer table and the lists' codes and ids are installed as read: nothing
+    is assigned or encoded again."""
+    idx = IndexIVFScalarQuantizer(None, z["d"], z["nlist"], z["qtype"], z["metric"], z["by_residual"], device)
+    if z["is_trained"]:
+        idx.set_trained(z["centroids"], z["trained"])
+        nonempty = [(l, ids, codes) for l, (ids, codes) in enumerate(z["lists"]) if len(ids)]
+        if nonempty:
+            idx.add_codes(np.concatenate([np.full(len(ids), l, np.int64) for l, ids, _ in nonempty]),
+                          np.concatenate([codes for _, _, codes in nonempty]),
+                          np.concatenate([ids for _, ids, _ in nonempty]))
+    idx.nprobe = max(1, min(int(z["nprobe"]), z["nlist"]))
+    return idx
+
+
 def _sq_from_dict(z, device):
     idx = IndexScalarQuantizer(z["d"], z["qtype"], z["metric"], device)
     if z["is_trained"]:
@@ -1754,13 +1907,15 @@ def _index_from_dict(z, device):
         return _flat_from_dict(z, device)
     if z["kind"] == "ivfflat":
         return _ivfflat_from_dict(z, device)
+    if z["kind"] == "ivfsq":
+        return _ivfsq_from_dict(z, device)
     if z["kind"] == "sq":
         return _sq_from_dict(z, device)
     return _pq_from_dict(z, device) if z["kind"] == "pq" else _ivfpq_from_dict(z, device)
 
 
 def read_index(path, device=None):
-    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexScalarQuantizer ("IxSQ") / IndexFlatL2 ("IxF2") / IndexFlatIP ("IxFI") / IndexPreTransform ("IxPT")
+    """Load a Faiss IndexIVFPQ ("IwPQ") / IndexPQ ("IxPq") / IndexIVFFlat ("IwFl") / IndexIVFScalarQuantizer ("IwSq") / IndexScalarQuantizer ("IxSQ") / IndexFlatL2 ("IxF2") / IndexFlatIP ("IxFI") / IndexPreTransform ("IxPT")
     file or a CHIVFPQ1 image onto ``device``."""
     device = _default_device() if device is None else device
     with open(path, "rb") as f:

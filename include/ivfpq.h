@@ -406,6 +406,75 @@ int ivfpq_sq_get_codes(ivfpq_sq_index* h, int64_t i0, int64_t n, uint8_t* out);
 int ivfpq_sq_encode(ivfpq_sq_index* h, int64_t n, const float* x, uint8_t* codes);
 int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x);
 
+/* ---- IVF over scalar-quantizer codes: faiss.IndexIVFScalarQuantizer(quantizer, d, nlist,
+ * qtype, metric, by_residual) -----------------------------------------------------------
+ * (the "IVF<nlist>,SQ8" / "IVF<nlist>,SQfp16" factory keys; with QT_fp16 and by_residual = 0
+ * what co.useFloat16 = True makes of an "IVF..,Flat" key in bench_gpu_1bn.py:575-578 and its
+ * siblings bench_gpu_1bn_SC.py, bench_gpu_performance_OSDI.py, gpu_infinite_loop.py).
+ * IndexIVFFlat's coarse quantizer, lists, adds and probe selection with the rows stored as
+ * IndexScalarQuantizer's codes (same three types, same formulas, the others rejected by name).
+ * by_residual: the codes encode x - centroid[list] (one fp32 subtraction per component, the list
+ * the coarse top-1) instead of x.  A search decodes every row y of every probed list:
+ *   L2   fvec_L2sqr(qr, y) in Faiss's AVX order with qr = q - centroid[list] when by_residual,
+ *        else qr = q;
+ *   IP   fvec_inner_product(q, y), plus the pair's coarse similarity when by_residual, as one
+ *        fp32 add (IVFSQScannerIP: accu0 = coarse_dis).
+ * So with by_residual = 0 a search equals IndexIVFFlat over the decoded vectors.  Training: the
+ * coarse k-means of ivfpq_ivfflat_train, then RS_minmax (rangestat_arg 0) over the first 100 000
+ * rows of the library's rand_perm(n, 1234) (all rows when n <= 100 000), replaced by their
+ * residuals when by_residual; QT_fp16 trains no table.  d must be a multiple of 4 in [4, 2048];
+ * nlist >= 1; nprobe is clamped to nlist; k <= 1024; fewer than 2^31 - 1 vectors.  Same
+ * conventions, errors and locking as above (one mutex per handle); device calls of one handle
+ * on different streams run one after the other.  The codes live in HBM only. */
+typedef struct ivfpq_ivfsq_index ivfpq_ivfsq_index;
+
+int ivfpq_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device,
+                       ivfpq_ivfsq_index** out);
+int ivfpq_ivfsq_free(ivfpq_ivfsq_index* h);
+/* Index.train(x): centroids as ivfpq_ivfflat_train (niter, seed), then the quantizer's table. */
+int ivfpq_ivfsq_train(ivfpq_ivfsq_index* h, int64_t n, const float* x, int niter, uint64_t seed);
+/* Install centroids [nlist][d] and sq.trained (count values: 2 d, 2 or 0, as ivfpq_sq_set_trained). */
+int ivfpq_ivfsq_set_trained(ivfpq_ivfsq_index* h, const float* centroids, const float* sq_trained, int64_t count);
+/* Index.add(x) / add_with_ids(x, ids); ids == NULL assigns ntotal, ntotal+1, ...  Assigned,
+ * reduced to the residual (by_residual) and encoded on the GPU. */
+int ivfpq_ivfsq_add(ivfpq_ivfsq_index* h, int64_t n, const float* x, const int64_t* ids);
+/* The same with x (and ids, nullable) in HBM, on `stream` (hipStream_t, NULL = the handle's
+ * stream); returns when the codes are in place. */
+int ivfpq_ivfsq_add_device(ivfpq_ivfsq_index* h, int64_t n, const float* x, const int64_t* ids, void* stream);
+/* Append precomputed codes uint8 [n][code_size] to the lists `lists` [n] with labels ids
+ * (nullable: sequential), e.g. the inverted lists of a loaded index file.  Host buffers. */
+int ivfpq_ivfsq_add_codes(ivfpq_ivfsq_index* h, int64_t n, const int64_t* lists, const uint8_t* codes,
+                          const int64_t* ids);
+/* Index.reset(): drop the codes, keep the centroids and the quantizer's table. */
+int ivfpq_ivfsq_reset(ivfpq_ivfsq_index* h);
+int ivfpq_ivfsq_set_nprobe(ivfpq_ivfsq_index* h, int nprobe); /* 1..1024, clamped to nlist at search */
+int ivfpq_ivfsq_get_nprobe(const ivfpq_ivfsq_index* h);
+/* Index.search(x, k) -> (D, I), host buffers. */
+int ivfpq_ivfsq_search(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* IndexIVF::search_preassigned.  Iq: int64 [n][nprobe] list ids (-1 = skip; a list id repeated
+ * in a row is scanned once, with the coarse value of its first column).  Dq [n][nprobe] is read
+ * for the inner product with by_residual only (NULL = zeros, as faiss.contrib.ivf_tools passes);
+ * otherwise it is accepted and ignored. */
+int ivfpq_ivfsq_search_preassigned(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
+                                   const float* Dq, float* D, int64_t* I);
+/* Device-pointer variants, launched on `stream` (hipStream_t, NULL = the default stream). */
+int ivfpq_ivfsq_search_device(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I,
+                              void* stream);
+int ivfpq_ivfsq_search_preassigned_device(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
+                                          const float* Dq, float* D, int64_t* I, void* stream);
+/* Accessors.  is_trained: centroids installed and (8-bit types) the quantizer's table. */
+int64_t ivfpq_ivfsq_ntotal(const ivfpq_ivfsq_index* h);
+int ivfpq_ivfsq_is_trained(const ivfpq_ivfsq_index* h);
+int ivfpq_ivfsq_get_dims(const ivfpq_ivfsq_index* h, int* d, int* nlist, int* qtype, int* metric, int* by_residual,
+                         int* code_size);
+int ivfpq_ivfsq_get_centroids(const ivfpq_ivfsq_index* h, float* out); /* [nlist][d] */
+/* sq.trained: *count = its length; out (nullable) receives the values */
+int ivfpq_ivfsq_get_trained(const ivfpq_ivfsq_index* h, float* out, int64_t* count);
+int ivfpq_ivfsq_get_list_sizes(ivfpq_ivfsq_index* h, int64_t* out); /* [nlist] (invlists.list_size) */
+/* invlists.get_codes / get_ids of one list, label-sorted: codes uint8 [size][code_size], ids
+ * int64 [size] (either nullable), copied from the device image. */
+int ivfpq_ivfsq_get_list(ivfpq_ivfsq_index* h, int list, uint8_t* codes, int64_t* ids);
+
 /* ---- flat binary codes: faiss.IndexBinaryFlat(d) -----------------------------------
  * (beir faiss_search.py BinaryFaissSearch: IndexBinaryFlat(dim * 8), binary_k = 1000
  * Hamming candidates, then a float re-rank).  d is in bits, a multiple of 8 in [8, 2048];

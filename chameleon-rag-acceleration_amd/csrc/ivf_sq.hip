@@ -10,15 +10,20 @@
 //    qr[query][probe][d] = q - centroid of every pair (by_residual, L2): the G query rows of an
 //    item then differ per list, and the scan reads them like any query row, wave-uniformly
 //    through the scalar cache (written by an earlier launch, so safe to read there);
-//  * k_ivfsq_scan is k_ivfflat_scan's item loop around k_sq_scan's pass (sq_scan.hip): a tile of
-//    256 rows x 64 dimensions of CODES staged in LDS with 16-byte loads, the next one in flight,
-//    rows padded to an odd number of 16-byte slots, one decode per row for all G queries, the
-//    8-bit unit[] table built with the real division.  A piece that straddles a row's end reads
-//    the next row's (the next list's) first bytes or, at the image's last row, its slack.
-//    For the inner product with by_residual the pair's coarse value is added to the folded sum
-//    before the key is formed.  The top-k holds image positions; labels are looked up at the write;
+//  * k_ivfsq_scan is k_ivfflat_scan's item loop around k_sq_scan's pass: a tile of 256 rows x 64
+//    dimensions of CODES staged in LDS with 16-byte loads, the next one in flight, rows padded to
+//    an odd number of 16-byte slots, one decode per row for all G queries, the 8-bit unit[] table
+//    built with the real division.  The tile layout, the vector types and the (G, R) classes are
+//    sq_pass.h's, shared with sq_scan.hip.  The item header and the pass are this file's own text,
+//    copies of k_ivfflat_scan's and of sq_pass.h's scan_code_rows: on shared helpers
+//    k_ivfflat_scan and this kernel each measured slower on two rows than the version before
+//    allows (profiles/ivf_shared_pass_refactor.md).  A piece that straddles a row's end reads the
+//    next row's (the next list's) first bytes or, at the image's last row, its slack.  For the
+//    inner product with by_residual the pair's coarse value is added to the folded sum before
+//    the key is formed.  The top-k holds image positions; labels are looked up at the write;
 //  * wave top-k, shared bound, LDS queues above k = 64 and the merge rounds are scan_topk.h's;
-//  * k_ivfsq_encode is sq_scan.hip's encode formula over x or x - centroid, one thread per component.
+//  * k_ivfsq_encode is sq_pass.h's encode of a component over x or x - centroid, one thread per
+//    component.
 // Compiled with -ffp-contract=off like the rest of the library.
 #include <float.h>
 #include <stdint.h>
@@ -29,16 +34,11 @@
 
 #include "ivf_sq.h"
 #include "scan_topk.h"
+#include "sq_pass.h"
 
 namespace chivf {
 
 namespace {
-
-using u4 = uint32_t __attribute__((ext_vector_type(4)));  // 16 bytes of codes, held in registers
-// a 16-byte global load of codes: rows are 4-byte (8-bit) or 8-byte (fp16) aligned only
-typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
-using h8 = _Float16 __attribute__((ext_vector_type(8)));
-using h4 = _Float16 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------ residuals, encode
 // one thread per component (out may alias x: per = 1, every thread reads what it writes)
@@ -68,34 +68,11 @@ __global__ __launch_bounds__(256) void k_ivfsq_encode(const float* __restrict__ 
       const int64_t l = lists[i];
       if (l >= 0 && l < nlist) v = v - cent[l * d + j];  // (a row assigned to no list fails the merge)
     }
-    if constexpr (CODEC == SQ_CODEC_FP16) {
-      reinterpret_cast<_Float16*>(codes)[gid] = (_Float16)v;  // round to nearest even, subnormals kept
-    } else {
-      const float vd = vdiff[j];
-      float xi = 0.f;
-      if (vd != 0.f) {
-        xi = (v - vmin[j]) / vd;
-        if (xi < 0.f) xi = 0.f;
-        if (xi > 1.f) xi = 1.f;
-      }
-      codes[gid] = (uint8_t)(int)(255.f * xi);
-    }
+    encode_component<CODEC>(v, j, vmin, vdiff, codes, gid);
   }
 }
 
 // ------------------------------------------------------------------------ scan
-constexpr int kDc = 64;     // dimensions per staged step (a multiple of 16): k_sq_scan's
-constexpr int kTile = 256;  // rows per pass: one per thread
-constexpr int kQ = kQueue<1>;  // queued candidates per (wave, query): one push per lane and pass
-
-template <int CODEC>
-struct Layout {
-  static constexpr int kElem = CODEC == SQ_CODEC_FP16 ? 2 : 1;  // bytes per dimension
-  static constexpr int kStepBytes = kDc * kElem;                // of a row's step: 128 / 64
-  static constexpr int kPieces = kStepBytes / 16;               // 16-byte pieces per row and step = loads per thread
-  static constexpr int kStride = kStepBytes + 16;               // bytes per LDS row: 144 / 80 (an odd number of 16-byte slots)
-};
-
 // Persistent over work items: workgroup b takes items b, b + gridDim.x, ...
 // xq: the query rows.  Pair g of an item reads row qid (probe_of null, or the inner product) or
 // row qid * nprobe + probe (probe_of set, L2: the residual queries).  cdis (inner product,
@@ -322,35 +299,26 @@ __global__ __launch_bounds__(256) void k_ivfsq_scan(const float* __restrict__ xq
   }
 }
 
-template <int KIND, int CODEC, int G, int R>
-void launch_scan(const IvfSqArgs& a, const IvfFlatPlan& p, const float* xq, hipStream_t s) {
-  const IvfFlatArgs& f = a.f;
-  hipLaunchKernelGGL((k_ivfsq_scan<KIND, CODEC, G, R>), dim3((unsigned)p.grid), dim3(256), 0, s, xq, f.nq, f.d, a.codes,
-                     f.ids, f.list_off, f.nlist, a.vmin, a.vdiff, f.cnt, f.bucket, f.item_off,
-                     a.by_residual ? a.probe_of : nullptr, f.nprobe, a.cdis, f.tau, f.k, p.S, f.partD, f.partI);
-}
-template <int KIND, int CODEC>
-void launch_scan_codec(const IvfSqArgs& a, const IvfFlatPlan& p, const float* xq, hipStream_t s) {
-  // k_sq_scan's classes: (G, R) = (8, 1) for fp16 and (4, 1) for 8-bit at k <= 64, (4, 4) for
-  // k <= 256, (4, 16) above (ivfsq_plan sets plan.G accordingly)
-  constexpr int kSmallG = CODEC == SQ_CODEC_8BIT ? 4 : 8;
-  if (a.f.k <= 64) launch_scan<KIND, CODEC, kSmallG, 1>(a, p, xq, s);
-  else if (a.f.k <= 256) launch_scan<KIND, CODEC, 4, 4>(a, p, xq, s);
-  else launch_scan<KIND, CODEC, 4, 16>(a, p, xq, s);
-}
-template <int KIND>
-void launch_scan_kind(const IvfSqArgs& a, const IvfFlatPlan& p, const float* xq, hipStream_t s) {
-  if (a.codec == SQ_CODEC_FP16) launch_scan_codec<KIND, SQ_CODEC_FP16>(a, p, xq, s);
-  else launch_scan_codec<KIND, SQ_CODEC_8BIT>(a, p, xq, s);
-}
-
-unsigned elementwise_grid(int64_t total) { return (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20); }
+// one (G, R) class of sq_pass.h's launch_scan
+struct ScanLaunch {
+  const IvfSqArgs& a;
+  const IvfFlatPlan& p;
+  const float* xq;
+  hipStream_t s;
+  template <int KIND, int CODEC, int G, int R>
+  void launch() const {
+    const IvfFlatArgs& f = a.f;
+    hipLaunchKernelGGL((k_ivfsq_scan<KIND, CODEC, G, R>), dim3((unsigned)p.grid), dim3(256), 0, s, xq, f.nq, f.d,
+                       a.codes, f.ids, f.list_off, f.nlist, a.vmin, a.vdiff, f.cnt, f.bucket, f.item_off,
+                       a.by_residual ? a.probe_of : nullptr, f.nprobe, a.cdis, f.tau, f.k, p.S, f.partD, f.partI);
+  }
+};
 
 }  // namespace
 
 IvfFlatPlan ivfsq_plan(int codec, int k, int64_t slots) {
   IvfFlatPlan p = ivfflat_plan(k, slots);
-  if (codec == SQ_CODEC_8BIT) p.G = 4;  // the 8-bit codec takes four pairs per item at every k
+  p.G = scan_group_for(codec, k);  // the classes of launch_scan
   return p;
 }
 
@@ -384,10 +352,7 @@ void launch_ivfsq_search(const IvfSqArgs& a, const IvfFlatPlan& p, hipStream_t s
     launch_ivfsq_residuals(f.x, f.nq * f.nprobe, f.nprobe, f.d, f.probes, a.cent, f.nlist, a.qr, s);
     xq = a.qr;
   }
-  if (f.ip)
-    launch_scan_kind<K_IP>(a, p, xq, s);
-  else
-    launch_scan_kind<K_L2>(a, p, xq, s);
+  launch_scan(f.ip, a.codec, f.k, ScanLaunch{a, p, xq, s});
   merge_partial_lists(f.partD, f.partI, f.tmpD, f.tmpI, p.S, p.fan, f.nq, f.k, f.ip, f.D, f.I, s);
 }
 

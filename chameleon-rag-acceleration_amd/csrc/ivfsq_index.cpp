@@ -1,22 +1,22 @@
 // IVF over scalar-quantizer codes (IndexIVFScalarQuantizer) behind the C-ABI of include/ivfpq.h.
 // faiss.IndexIVFScalarQuantizer: IVF-Flat's coarse quantizer, device list image and pending-add
-// merge (ivfflat_index.cpp) with the rows stored as the flat scalar quantizer's fp16 / 8-bit
-// codes (sq_index.cpp), of the vector or, by_residual, of the vector minus its list's
-// centroid; scanned by ivf_sq.hip.  The codes live only in the device image {list_off, codes,
-// ids}, every list sorted by label, with the scan's read slack behind the last row; adds are
-// encoded straight into a pending set on the device and merged with the image kernels of
-// ivfpq_build.h at code size d or 2 d.  Device calls on different streams are ordered one
-// after the other (one workspace per handle).
+// merge with the rows stored as the flat scalar quantizer's fp16 / 8-bit codes (sq_index.cpp),
+// of the vector or, by_residual, of the vector minus its list's centroid; scanned by
+// ivf_sq.hip.  The codes live only in the device image {list_off, codes, ids}, every list
+// sorted by label, with the scan's read slack behind the last row; adds are encoded straight
+// into a pending set on the device and merged with the image kernels of ivfpq_build.h at code
+// size d or 2 d.  The handle -- image, pending set, workspaces, the search around the scan and
+// the entry points that IVF-Flat has too -- is ivf_lists.h's IvfLists; this file keeps the
+// codes: the quantizer's table and its training, the encoding adds, the by_residual
+// workspaces, the scan's launch, create and the entry points' names.
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <vector>
 
-#include "coarse_quantizer.h"
+#include "ivf_lists.h"
 #include "ivf_sq.h"
 #include "ivfpq.h"
 #include "kmeans.h"
-#include "list_image.h"
 #include "sq_params.h"
 
 using namespace chivf;
@@ -26,74 +26,53 @@ constexpr int64_t kSqTrainRows = 100000;  // ScalarQuantizer::train_residual's s
 constexpr uint64_t kSqTrainSeed = 1234;   // ... and its rand_perm seed
 }  // namespace
 
-struct ivfpq_ivfsq_index : StreamOrder {
-  int d = 0, nlist = 0, qtype = IVFPQ_SQ_FP16, metric = IVFPQ_METRIC_L2, device = 0;
+struct ivfpq_ivfsq_index : IvfLists {
+  int qtype = IVFPQ_SQ_FP16;
   int codec = SQ_CODEC_FP16, code_size = 0;
   bool by_residual = true;
-  int nprobe = 1;
-  bool cent_trained = false, sq_trained = false;
-  std::vector<float> centroids;  // [nlist][d]
-  std::vector<float> params;     // Faiss's sq.trained
-  CoarseQuantizer cq;
-  CoarseScratch cw;
+  bool sq_trained = false;
+  std::vector<float> params;  // Faiss's sq.trained
   DevBuf d_vmin, d_vdiff;
-  int64_t ntotal = 0, next_id = 0;
-  int64_t img_n = 0;  // codes in the image (ntotal = img_n + q.n)
-  ListImage img;
-  std::vector<int64_t> h_off;      // the image's list offsets
-  std::vector<int64_t> range_top;  // range_top[p] = row ranges of the p longest lists (the slot bound)
-  PendingSet q;                    // pending adds: list numbers, labels, codes
-  DevBuf w_D, w_x, w_xa, w_mm, h_D, h_I, h_Iq, h_Dq;  // add / train scratch; staging of the host entry points
-  DevBuf w_lists, w_dis, w_cd, p_cnt, p_bucket, p_probe, p_qr, p_items, p_used, p_tau, p_partD, p_partI, p_tmpD,
-      p_tmpI;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
+  DevBuf w_xa, w_mm;               // add / train staging
+  DevBuf w_cd, p_probe, p_qr;      // by_residual: zero coarse values, probe columns, residual queries
 
-  ~ivfpq_ivfsq_index() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
-  bool trained() const { return cent_trained && sq_trained; }
-  size_t row_bytes() const { return q.row_bytes; }
+  bool trained() const override { return cent_trained && sq_trained; }
+  bool resid_q() const { return by_residual && !ip(); }     // residual queries
+  bool coarse_add() const { return by_residual && ip(); }   // the pair's coarse value added
 
-  void upload_centroids() {
-    quiesce();
-    cq.upload(centroids.data(), stream);
-    cent_trained = true;
+  IvfFlatPlan plan(int k, int64_t slots) const override { return ivfsq_plan(codec, k, slots); }
+  // the probe column of every bucket entry beside the coarse keys and buckets
+  size_t entry_bytes() const override { return by_residual ? 12 : 8; }
+  // the [c][np][d] residual queries within kChunkBytes
+  int64_t prepare_chunks(int64_t qc, int np, bool zero_coarse, hipStream_t s) override {
+    if (resid_q()) qc = std::max<int64_t>(1, std::min<int64_t>(qc, (int64_t)(kChunkBytes / (sizeof(float) * np * d))));
+    if (coarse_add() && zero_coarse) {
+      w_cd.ensure(sizeof(float) * qc * np);
+      HIPCHECK(hipMemsetAsync(w_cd.p, 0, sizeof(float) * qc * np, s));
+    }
+    if (by_residual) p_probe.ensure(sizeof(int32_t) * (size_t)nlist * qc);
+    if (resid_q()) p_qr.ensure(sizeof(float) * (size_t)qc * np * d);
+    return qc;
   }
+  void launch_chunk(const IvfFlatArgs& f, const IvfFlatPlan& pl, const float* cdis, hipStream_t s) override {
+    IvfSqArgs a;
+    a.f = f;
+    a.cdis = coarse_add() ? (cdis ? cdis : w_cd.as<float>()) : nullptr;
+    a.codec = codec;
+    a.codes = img.rows.as<uint8_t>();
+    a.vmin = d_vmin.as<float>();
+    a.vdiff = d_vdiff.as<float>();
+    a.by_residual = by_residual;
+    a.cent = cq.d_cent.as<float>();
+    a.probe_of = p_probe.as<int32_t>();
+    a.qr = p_qr.as<float>();
+    launch_ivfsq_search(a, pl, s);
+  }
+
   void upload_params() {
     quiesce();
     if (codec == SQ_CODEC_8BIT) sq_upload_params(params, qtype, d, d_vmin, d_vdiff, stream);
     sq_trained = true;
-  }
-
-  void set_offsets(std::vector<int64_t> off) {
-    h_off = std::move(off);
-    std::vector<int64_t> r(nlist);
-    for (int l = 0; l < nlist; l++) r[l] = (h_off[l + 1] - h_off[l] + kIvfFlatRangeRows - 1) / kIvfFlatRangeRows;
-    std::sort(r.begin(), r.end(), std::greater<int64_t>());
-    range_top.assign(nlist + 1, 0);
-    for (int l = 0; l < nlist; l++) range_top[l + 1] = range_top[l] + r[l];
-  }
-
-  // an empty image (create, reset)
-  void clear_image() {
-    quiesce();
-    q.drop();
-    img.rows.release();
-    img.ids.release();
-    img.off.ensure(sizeof(int64_t) * (nlist + 1));
-    HIPCHECK(hipMemsetAsync(img.off.p, 0, sizeof(int64_t) * (nlist + 1), stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    set_offsets(std::vector<int64_t>(nlist + 1, 0));
-    img_n = ntotal = next_id = 0;
-  }
-
-  // rows per pass of add and train: the [rows][nlist] coarse keys and the [rows][d] staging within kChunkBytes
-  int64_t chunk_rows(int64_t n) const {
-    const int64_t by_keys =
-        nlist >= kSegmentedNlist ? (int64_t)1 << 18 : (int64_t)(kChunkBytes / ((size_t)nlist * 4));
-    return std::max<int64_t>(1, std::min<int64_t>({n, by_keys, (int64_t)(kChunkBytes / (sizeof(float) * d))}));
   }
 
   // The scalar quantizer's table: RS_minmax (rangestat_arg 0) over the first kSqTrainRows rows of
@@ -108,7 +87,7 @@ struct ivfpq_ivfsq_index : StreamOrder {
     std::vector<int64_t> pick;
     if (n > kSqTrainRows) pick = rand_perm_prefix(n, kSqTrainRows, kSqTrainSeed);
     const int64_t m = pick.empty() ? n : (int64_t)pick.size();
-    const int64_t rows = chunk_rows(m);
+    const int64_t rows = chunk_rows(m, true);
     w_xa.ensure(sizeof(float) * rows * d);
     w_mm.ensure(sizeof(uint32_t) * 2 * d);
     if (by_residual) {
@@ -144,35 +123,13 @@ struct ivfpq_ivfsq_index : StreamOrder {
     upload_params();
   }
 
-  void reserve_pending(int64_t n, hipStream_t s) {
-    require(ntotal + n < (int64_t)INT32_MAX, "IndexIVFScalarQuantizer holds fewer than 2^31 - 1 vectors");
-    order_after(s);
-    quiesce();
-    q.reserve(q.n + n, s);
-  }
-  void commit_pending(int64_t n, hipStream_t s) {
-    HIPCHECK(hipStreamSynchronize(s));
-    q.n += n;
-    ntotal += n;
-    if (q.n >= std::max<int64_t>(img_n, (int64_t)(kChunkBytes / row_bytes()))) flush_pending(s);
-  }
-  void pending_ids(int64_t n, const int64_t* ids, bool ids_on_device, hipStream_t s) {
-    if (!ids) {
-      launch_iota_i64(q.ids.as<int64_t>() + q.n, n, next_id, s);
-      next_id += n;
-    } else {
-      HIPCHECK(hipMemcpyAsync(q.ids.as<int64_t>() + q.n, ids, sizeof(int64_t) * n,
-                              ids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    }
-  }
-
   // n vectors (host or device) into the pending set: assigned by the search's coarse kernels
   // (top-1) and encoded there, pass by pass.  Merged into the image before the lists are
   // next read, or once the pending set is as large as the image (and at least kChunkBytes).
   void add_dev(int64_t n, const float* x, bool x_on_device, const int64_t* ids, bool ids_on_device, hipStream_t s) {
     if (n <= 0) return;
     reserve_pending(n, s);
-    const int64_t rows = chunk_rows(n);
+    const int64_t rows = chunk_rows(n, true);
     if (!x_on_device) w_xa.ensure(sizeof(float) * rows * d);
     w_D.ensure(sizeof(float) * rows);
     int64_t* lists = q.lists.as<int64_t>() + q.n;
@@ -204,175 +161,25 @@ struct ivfpq_ivfsq_index : StreamOrder {
     pending_ids(n, ids, false, stream);
     commit_pending(n, stream);
   }
-
-  // the pending codes merged into the image (merge_pending with code_size bytes as the row;
-  // the new image is allocated with the scan's slack behind its last row)
-  void flush_pending(hipStream_t s) {
-    if (q.n == 0) return;
-    quiesce();
-    set_offsets(merge_pending(q, img, nlist, 0, nlist, h_off.data(), q.n,
-                              "pending merge: a vector was assigned to no list", s));
-    img_n = h_off[nlist];
-    require(img_n == ntotal, "pending merge: image size disagrees with ntotal");
-  }
-
-  // The search on device pointers, on stream s.  Iq non-null = preassigned probes [n][nprobe]
-  // (the handle's nprobe) with their coarse values Dq (read for the inner product with
-  // by_residual only; null = zeros).
-  void search_dev(int64_t n, const float* x, int k, float* D, int64_t* I, const int64_t* Iq, const float* Dq,
-                  hipStream_t s) {
-    flush_pending(s);
-    if (n == 0) return;
-    order_after(s);
-    if (img_n == 0) {
-      launch_fill_empty(D, I, n * k, ip(), s);
-      HIPCHECK(hipGetLastError());
-      mark_done(s);
-      return;
-    }
-    const int np = Iq ? nprobe : std::min(nprobe, nlist);
-    const IvfFlatPlan pl = ivfsq_plan(codec, k, range_top[std::min(np, nlist)]);
-    const bool resid_q = by_residual && !ip();  // residual queries
-    const bool coarse_add = by_residual && ip();  // the pair's coarse value added
-    // queries per chunk: the [c][nlist] coarse keys, buckets and probe columns and the
-    // [c][np][d] residual queries within kChunkBytes each, the partial lists (12 bytes per
-    // entry, and the first merge round's output) within kPartialBytes
-    const size_t part_q = (size_t)pl.S * k * 12 * 2;
-    int64_t qc = std::max<int64_t>(
-        1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)nlist * (by_residual ? 12 : 8))),
-                              (int64_t)(kPartialBytes / part_q), (int64_t)(INT32_MAX / 2) / ((int64_t)pl.S * k)}));
-    if (resid_q) qc = std::max<int64_t>(1, std::min<int64_t>(qc, (int64_t)(kChunkBytes / (sizeof(float) * np * d))));
-    if (!Iq) {
-      w_lists.ensure(sizeof(int64_t) * qc * np);
-      w_dis.ensure(sizeof(float) * qc * np);
-    } else if (coarse_add && !Dq) {
-      w_cd.ensure(sizeof(float) * qc * np);
-      HIPCHECK(hipMemsetAsync(w_cd.p, 0, sizeof(float) * qc * np, s));
-    }
-    p_cnt.ensure(sizeof(int32_t) * nlist);
-    p_bucket.ensure(sizeof(int2) * (size_t)nlist * qc);
-    if (by_residual) p_probe.ensure(sizeof(int32_t) * (size_t)nlist * qc);
-    if (resid_q) p_qr.ensure(sizeof(float) * (size_t)qc * np * d);
-    p_items.ensure(sizeof(int32_t) * (nlist + 1));
-    p_used.ensure(sizeof(int32_t) * qc);
-    p_tau.ensure(sizeof(uint32_t) * qc);
-    p_partD.ensure(sizeof(float) * (size_t)pl.S * qc * k);
-    p_partI.ensure(sizeof(int64_t) * (size_t)pl.S * qc * k);
-    const size_t tmp_lists = (size_t)std::max(1, pl.S / pl.fan);
-    p_tmpD.ensure(sizeof(float) * tmp_lists * qc * k);
-    p_tmpI.ensure(sizeof(int64_t) * tmp_lists * qc * k);
-    for (int64_t q0 = 0; q0 < n; q0 += qc) {
-      const int64_t c = std::min(qc, n - q0);
-      const float* xq = x + q0 * d;
-      IvfSqArgs a;
-      IvfFlatArgs& f = a.f;
-      f.x = xq;
-      f.nq = c;
-      f.d = d;
-      f.vecs = nullptr;
-      f.ids = img.ids.as<int64_t>();
-      f.list_off = img.off.as<int64_t>();
-      f.nlist = nlist;
-      a.cdis = nullptr;
-      if (Iq) {
-        f.probes = Iq + q0 * np;
-        if (coarse_add) a.cdis = Dq ? Dq + q0 * np : w_cd.as<float>();
-      } else {
-        cq.launch(cw, xq, c, np, w_dis.as<float>(), w_lists.as<int64_t>(), s);
-        f.probes = w_lists.as<int64_t>();
-        if (coarse_add) a.cdis = w_dis.as<float>();
-      }
-      f.nprobe = np;
-      f.dedup = Iq != nullptr;
-      f.k = k;
-      f.ip = ip();
-      f.cnt = p_cnt.as<int32_t>();
-      f.bucket = p_bucket.as<int2>();
-      f.item_off = p_items.as<int32_t>();
-      f.used = p_used.as<int32_t>();
-      f.tau = p_tau.as<uint32_t>();
-      f.partD = p_partD.as<float>();
-      f.partI = p_partI.as<int64_t>();
-      f.tmpD = p_tmpD.as<float>();
-      f.tmpI = p_tmpI.as<int64_t>();
-      f.D = D + q0 * k;
-      f.I = I + q0 * k;
-      a.codec = codec;
-      a.codes = img.rows.as<uint8_t>();
-      a.vmin = d_vmin.as<float>();
-      a.vdiff = d_vdiff.as<float>();
-      a.by_residual = by_residual;
-      a.cent = cq.d_cent.as<float>();
-      a.probe_of = p_probe.as<int32_t>();
-      a.qr = p_qr.as<float>();
-      launch_ivfsq_search(a, pl, s);
-      HIPCHECK(hipGetLastError());
-    }
-    mark_done(s);
-  }
-
-  // host-buffer search (copies in and out on the handle's stream)
-  void search_host(int64_t n, const float* x, int k, float* D, int64_t* I, const int64_t* Iq, const float* Dq) {
-    if (n == 0) return;
-    quiesce();
-    w_x.ensure(sizeof(float) * n * d);
-    h_D.ensure(sizeof(float) * n * k);
-    h_I.ensure(sizeof(int64_t) * n * k);
-    HIPCHECK(hipMemcpyAsync(w_x.p, x, sizeof(float) * n * d, hipMemcpyHostToDevice, stream));
-    if (Iq) {
-      h_Iq.ensure(sizeof(int64_t) * n * nprobe);
-      HIPCHECK(hipMemcpyAsync(h_Iq.p, Iq, sizeof(int64_t) * n * nprobe, hipMemcpyHostToDevice, stream));
-    }
-    if (Iq && Dq) {
-      h_Dq.ensure(sizeof(float) * n * nprobe);
-      HIPCHECK(hipMemcpyAsync(h_Dq.p, Dq, sizeof(float) * n * nprobe, hipMemcpyHostToDevice, stream));
-    }
-    search_dev(n, w_x.as<float>(), k, h_D.as<float>(), h_I.as<int64_t>(), Iq ? h_Iq.as<int64_t>() : nullptr,
-               Iq && Dq ? h_Dq.as<float>() : nullptr, stream);
-    HIPCHECK(hipMemcpyAsync(D, h_D.p, sizeof(float) * n * k, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipMemcpyAsync(I, h_I.p, sizeof(int64_t) * n * k, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-  }
 };
-
-namespace {
-// the search arguments, in the words of ivfpq_search
-void check_ivfsq_search(const ivfpq_ivfsq_index* h, int64_t n, const void* x, int k, const void* D, const void* I) {
-  check_search_args(h->trained(), n, k);
-  require(n == 0 || (x && D && I), "null buffer");
-}
-}  // namespace
 
 extern "C" {
 
 int ivfpq_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device,
                        ivfpq_ivfsq_index** out) {
   return guarded([&] {
-    require(out != nullptr, "null output pointer");
-    require(d >= 4 && d <= 2048 && d % 4 == 0,
-            "IndexIVFScalarQuantizer: d must be a multiple of 4 in [4, 2048] (d = " + std::to_string(d) + ")");
-    require(nlist >= 1, "nlist must be >= 1");
+    check_ivf_create("IndexIVFScalarQuantizer", out, d, nlist);
     check_sq_qtype(qtype);
-    require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
-    int ndev = 0;
-    HIPCHECK(hipGetDeviceCount(&ndev));
-    require(device >= 0 && device < ndev, "device ordinal out of range");
+    check_ivf_device(metric, device);
     DeviceGuard g(device);
     auto h = std::make_unique<ivfpq_ivfsq_index>();
-    h->d = h->cq.d = d;
-    h->nlist = h->cq.nlist = nlist;
-    h->metric = h->cq.metric = metric;
     h->qtype = qtype;
     h->codec = sq_codec_of(qtype);
     h->code_size = sq_code_size(h->codec, d);
     h->by_residual = by_residual != 0;
-    h->device = device;
-    h->q.row_bytes = (size_t)h->code_size;
-    h->q.image_slack = kSqScanSlack;  // the scan's 16-byte loads may straddle the last row's end
     h->sq_trained = qtype == IVFPQ_SQ_FP16;  // no table to train
-    HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->create();
-    h->clear_image();
+    // (the scan's 16-byte loads may straddle the last row's end: kSqScanSlack)
+    h->open("IndexIVFScalarQuantizer", d, nlist, metric, device, (size_t)h->code_size, kSqScanSlack);
     *out = h.release();
   });
 }
@@ -434,55 +241,32 @@ int ivfpq_ivfsq_add_codes(ivfpq_ivfsq_index* h, int64_t n, const int64_t* lists,
   });
 }
 
-int ivfpq_ivfsq_reset(ivfpq_ivfsq_index* h) {
-  return with_handle(h, [&] { h->clear_image(); });
-}
+int ivfpq_ivfsq_reset(ivfpq_ivfsq_index* h) { return ivf_reset(h); }
 
-int ivfpq_ivfsq_set_nprobe(ivfpq_ivfsq_index* h, int nprobe) {
-  return guarded([&] {
-    check_handle(h);
-    require(nprobe >= 1 && nprobe <= kMaxK, "nprobe must be in [1, " + std::to_string(kMaxK) + "]");
-    h->nprobe = nprobe;
-  });
-}
+int ivfpq_ivfsq_set_nprobe(ivfpq_ivfsq_index* h, int nprobe) { return ivf_set_nprobe(h, nprobe); }
 
-int ivfpq_ivfsq_get_nprobe(const ivfpq_ivfsq_index* h) { return h ? h->nprobe : -1; }
+int ivfpq_ivfsq_get_nprobe(const ivfpq_ivfsq_index* h) { return ivf_get_nprobe(h); }
 
 int ivfpq_ivfsq_search(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I) {
-  return with_handle(h, [&] {
-    check_ivfsq_search(h, n, x, k, D, I);
-    h->search_host(n, x, k, D, I, nullptr, nullptr);
-  });
+  return ivf_search(h, n, x, k, D, I);
 }
 
 int ivfpq_ivfsq_search_preassigned(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
                                    const float* Dq, float* D, int64_t* I) {
-  return with_handle(h, [&] {
-    check_ivfsq_search(h, n, x, k, D, I);
-    require(n == 0 || Iq, "null Iq");
-    for (int64_t i = 0; i < n * h->nprobe; i++) require(Iq[i] < h->nlist, "list id out of range in Iq");
-    h->search_host(n, x, k, D, I, Iq, Dq);
-  });
+  return ivf_search_preassigned(h, n, x, k, Iq, Dq, D, I);
 }
 
 int ivfpq_ivfsq_search_device(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, float* D, int64_t* I,
                               void* stream) {
-  return with_handle(h, [&] {
-    check_ivfsq_search(h, n, x, k, D, I);
-    h->search_dev(n, x, k, D, I, nullptr, nullptr, (hipStream_t)stream);
-  });
+  return ivf_search_device(h, n, x, k, D, I, stream);
 }
 
 int ivfpq_ivfsq_search_preassigned_device(ivfpq_ivfsq_index* h, int64_t n, const float* x, int k, const int64_t* Iq,
                                           const float* Dq, float* D, int64_t* I, void* stream) {
-  return with_handle(h, [&] {
-    check_ivfsq_search(h, n, x, k, D, I);
-    require(n == 0 || Iq, "null Iq");
-    h->search_dev(n, x, k, D, I, n ? Iq : nullptr, Dq, (hipStream_t)stream);
-  });
+  return ivf_search_preassigned_device(h, n, x, k, Iq, Dq, D, I, stream);
 }
 
-int64_t ivfpq_ivfsq_ntotal(const ivfpq_ivfsq_index* h) { return h ? h->ntotal : -1; }
+int64_t ivfpq_ivfsq_ntotal(const ivfpq_ivfsq_index* h) { return ivf_ntotal(h); }
 
 int ivfpq_ivfsq_is_trained(const ivfpq_ivfsq_index* h) { return h && h->trained() ? 1 : 0; }
 
@@ -499,14 +283,7 @@ int ivfpq_ivfsq_get_dims(const ivfpq_ivfsq_index* h, int* d, int* nlist, int* qt
   });
 }
 
-int ivfpq_ivfsq_get_centroids(const ivfpq_ivfsq_index* h, float* out) {
-  return guarded([&] {
-    check_handle(h);
-    require(h->cent_trained, "index is not trained");
-    require(out != nullptr, "null output pointer");
-    std::memcpy(out, h->centroids.data(), sizeof(float) * h->centroids.size());
-  });
-}
+int ivfpq_ivfsq_get_centroids(const ivfpq_ivfsq_index* h, float* out) { return ivf_get_centroids(h, out); }
 
 int ivfpq_ivfsq_get_trained(const ivfpq_ivfsq_index* h, float* out, int64_t* count) {
   return guarded([&] {
@@ -517,28 +294,10 @@ int ivfpq_ivfsq_get_trained(const ivfpq_ivfsq_index* h, float* out, int64_t* cou
   });
 }
 
-int ivfpq_ivfsq_get_list_sizes(ivfpq_ivfsq_index* h, int64_t* out) {
-  return with_handle(h, [&] {
-    require(out != nullptr, "null output pointer");
-    h->flush_pending(h->stream);
-    for (int l = 0; l < h->nlist; l++) out[l] = h->h_off[l + 1] - h->h_off[l];
-  });
-}
+int ivfpq_ivfsq_get_list_sizes(ivfpq_ivfsq_index* h, int64_t* out) { return ivf_get_list_sizes(h, out); }
 
 int ivfpq_ivfsq_get_list(ivfpq_ivfsq_index* h, int list, uint8_t* codes, int64_t* ids) {
-  return with_handle(h, [&] {
-    require(list >= 0 && list < h->nlist, "list id out of range");
-    h->flush_pending(h->stream);
-    h->quiesce();
-    const int64_t b = h->h_off[list], n = h->h_off[list + 1] - b;
-    if (n == 0) return;
-    if (codes)
-      HIPCHECK(hipMemcpyAsync(codes, h->img.rows.as<uint8_t>() + b * h->code_size, h->row_bytes() * n,
-                              hipMemcpyDeviceToHost, h->stream));
-    if (ids)
-      HIPCHECK(hipMemcpyAsync(ids, h->img.ids.as<int64_t>() + b, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-  });
+  return ivf_get_list(h, list, codes, ids);
 }
 
 }  // extern "C"

@@ -1,12 +1,13 @@
-// Device code shared by the flat scans (pq_flat.hip, ivf_flat.hip, sq_scan.hip): the wave
-// top-k in registers over (key, int32 position) pairs, the per-query shared bound of the
-// exact scans, the LDS candidate queue of k > 64, the tail of a scan pass (distance
+// Device code shared by the flat scans (pq_flat.hip, ivf_flat.hip, sq_scan.hip, ivf_sq.hip):
+// the wave top-k in registers over (key, int32 position) pairs, the per-query shared bound of
+// the exact scans, the LDS candidate queue of k > 64, the tail of a scan pass (distance
 // terms, the fold to a key, admission, drain sites, the sorted write) and the host loop
 // that merges the exact scans' sorted partial lists in rounds.  k_pq_scan and
-// k_ivfflat_scan take their pass tail from here; k_sq_scan uses the top-k, the bound and
-// the queue but spells its tail out, because it measured slower on the helpers
-// (profiles/flat_scans_refactor.md).  Everything is in an anonymous namespace: each
-// translation unit compiles its own copy, inlined into its kernels.
+// k_ivfflat_scan take their pass tail from here, and k_ivfsq_scan its drain sites and write;
+// k_sq_scan's pass (sq_pass.h) uses the top-k, the bound and the queue but spells its tail out,
+// because it measured slower on the helpers (profiles/flat_scans_refactor.md).
+// Everything is in an anonymous namespace: each translation unit compiles its own copy,
+// inlined into its kernels.
 #pragma once
 #include <float.h>
 #include <stdint.h>
@@ -27,6 +28,8 @@ constexpr int kNone = INT32_MAX;  // "no candidate" position (real positions are
 enum { K_IP = 0, K_L2 = 1 };
 
 inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+// workgroups of 256 threads of a one-thread-per-component kernel that strides over `total`
+inline unsigned elementwise_grid(int64_t total) { return (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20); }
 
 // rows of 64 lanes in a wave's top-k: the three k classes of every flat scan
 inline int scan_rows_for(int k) { return k <= 64 ? 1 : k <= 256 ? 4 : 16; }

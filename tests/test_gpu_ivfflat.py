@@ -265,6 +265,36 @@ def test_adds_build_the_same_label_sorted_lists(metric):
                                   np.arange(100))
 
 
+def test_add_device_with_ids_past_the_pending_threshold():
+    """Exercises the add that merges its own pending set: one as large as the image and of at
+    least 256 MiB (kChunkBytes of csrc/host_common.h); 32768 vectors of d = 2048 are the fewest
+    that reach it.  Device vectors and device labels; a later small add then waits beside the
+    image.  The test cannot see when the merge ran (reading the lists merges whatever is
+    pending): it checks that the lists are right after this sequence, not that the add merged.
+    Rows sit 0.01 around centroids 10 apart, so the expected lists need no reference search."""
+    import torch
+
+    d, nlist, nb, extra = 2048, 4, (256 << 20) // (4 * 2048), 10
+    cent = np.zeros((nlist, d), np.float32)
+    cent[np.arange(nlist), np.arange(nlist)] = 10.0
+    g = torch.Generator(device="cuda").manual_seed(5)
+    n = nb + extra
+    lists = torch.arange(n, device="cuda") % nlist
+    tx = torch.from_numpy(cent).cuda()[lists] + 0.01 * torch.randn((n, d), generator=g, device="cuda")
+    tid = 3 * torch.arange(n - 1, -1, -1, dtype=torch.int64, device="cuda") + 7  # decreasing: label order != add order
+    ix = faiss.IndexIVFFlat(None, d, nlist, L2)
+    ix.set_trained(cent)
+    ix.add_device(tx[:nb], tid[:nb])
+    ix.add_device(tx[nb:], tid[nb:])
+    assert ix.ntotal == n
+    np.testing.assert_array_equal(ix.invlists.list_sizes(), np.bincount(lists.cpu().numpy(), minlength=nlist))
+    for l in range(nlist):
+        rows = torch.nonzero(lists == l).flatten().flip(0)  # the list's rows by increasing label
+        np.testing.assert_array_equal(ix.invlists.get_ids(l), tid[rows].cpu().numpy())
+        if l == 1:
+            assert ix.invlists.get_codes(l).tobytes() == tx[rows].cpu().numpy().tobytes()
+
+
 # -------------------------------------------------------------------- training
 @pytest.mark.parametrize("metric", METRICS)
 def test_training_is_the_coarse_kmeans_of_ivfpq(metric):

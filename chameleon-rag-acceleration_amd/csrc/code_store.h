@@ -76,7 +76,7 @@ struct CodeStore : StreamOrder {
 
   // rows per chunk of n host rows of in_bytes each that pass through a staging buffer
   static int64_t host_rows(int64_t n, size_t in_bytes) {
-    return std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / in_bytes));
+    return scratch_rows(n, in_bytes);
   }
 
   // n host rows of in_bytes each, staged chunk by chunk in w_x; add(c) puts the c staged

@@ -19,9 +19,7 @@ int64_t flat_query_chunk(int64_t n, int64_t nb, int k, int64_t force, FlatScanPl
   int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, 1 << 16));
   FlatScanPlan pl = flat_scan_plan(qc, nb, k, force);
   while (true) {
-    const size_t per_q = (size_t)pl.S * k * 12 * 2;
-    const int64_t lim =
-        std::max<int64_t>(1, std::min<int64_t>((int64_t)(kPartialBytes / per_q), (int64_t)(INT32_MAX / 2) / ((int64_t)pl.S * k)));
+    const int64_t lim = partial_list_queries(pl.S, k);
     if (qc <= lim) break;
     qc = std::max<int64_t>(1, std::min(lim, qc / 2));
     pl = flat_scan_plan(qc, nb, k, force);  // fewer query tiles: more ranges

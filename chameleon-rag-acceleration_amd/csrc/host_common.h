@@ -73,6 +73,65 @@ constexpr size_t kPartialBytes = size_t(2048) << 20;  // bound for a chunk's per
 // matrix 17.8 + 10.0 us with T3 in the same launch)
 constexpr int kSegmentedNlist = 8192;
 
+// ---- how the host cuts a batch ("Host-side splits") ------------------------
+// Every loop that takes a batch chunk by chunk asks one of these for its chunk, and so
+// does the getter that reports the cut to a test (ivfpq_*_get_*): host arithmetic only.
+
+// rows of n that pass at a time through a scratch buffer of kChunkBytes, row_bytes each
+inline int64_t scratch_rows(int64_t n, size_t row_bytes) {
+  return std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(kChunkBytes / row_bytes)));
+}
+
+// queries whose S sorted partial lists of k entries (12 bytes per entry, and the first merge
+// round's output) stay within kPartialBytes, their count within the merge's 32-bit indexing
+inline int64_t partial_list_queries(int S, int k) {
+  const size_t part_q = (size_t)S * k * 12 * 2;
+  return std::max<int64_t>(
+      1, std::min<int64_t>((int64_t)(kPartialBytes / part_q), (int64_t)(INT32_MAX / 2) / ((int64_t)S * k)));
+}
+
+// queries per chunk of a search whose scan leaves S partial lists per query (IndexScalarQuantizer)
+inline int64_t partial_query_chunk(int64_t n, int S, int k) {
+  return std::max<int64_t>(1, std::min<int64_t>(n, partial_list_queries(S, k)));
+}
+
+// queries per chunk of an IVF list-scan search (ivf_lists.h): the [c][nlist] coarse keys, buckets
+// and what the row type keeps per entry (entry_bytes in all) within kChunkBytes, the partial
+// lists as above, and where residual queries are kept their [c][np][d] floats within kChunkBytes
+inline int64_t ivf_query_chunk(int64_t n, int nlist, size_t entry_bytes, int S, int k, int np, int d,
+                               bool resid_queries) {
+  int64_t qc = std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)nlist * entry_bytes)), partial_list_queries(S, k)});
+  if (resid_queries) qc = std::min<int64_t>(qc, (int64_t)(kChunkBytes / (sizeof(float) * np * d)));
+  return std::max<int64_t>(1, qc);
+}
+
+// queries per chunk of an IVF-PQ search: the [c][nlist] keys, T3 ([c][M][ksub]) and the buckets of
+// the handle's nloc lists within kChunkBytes; the per-wave partial lists ([c][np][4][k] 16-byte
+// records: 64 bytes per entry and query) within kPartialBytes, so large k still runs whole
+// 1024-query batches (C3, k = 1000, nprobe 32: 2 MB per query)
+inline int64_t ivfpq_query_chunk(int64_t n, int nlist, int M, int ksub, int nloc, int np, int k) {
+  const size_t per_q = std::max({(size_t)nlist * 4, (size_t)M * ksub * 4, (size_t)std::max(nloc, 1) * 16});
+  return std::max<int64_t>(
+      1, std::min<int64_t>({n, (int64_t)(kChunkBytes / per_q), (int64_t)(kPartialBytes / ((size_t)np * part_stride(k) * 64))}));
+}
+
+// rows per pass of an IVF add or training pass: the [rows][nlist] coarse keys within kChunkBytes
+// (2^18 rows where the coarse quantizer writes no key matrix), and a [rows][d] fp32 staging
+// buffer where the pass has one
+inline int64_t ivf_pass_rows(int64_t n, int nlist, int d, bool staged) {
+  int64_t rows = nlist >= kSegmentedNlist ? (int64_t)1 << 18 : (int64_t)(kChunkBytes / ((size_t)nlist * 4));
+  if (staged) rows = std::min<int64_t>(rows, (int64_t)(kChunkBytes / (sizeof(float) * d)));
+  return std::max<int64_t>(1, std::min(n, rows));
+}
+
+// rows per pass of a k-means assignment: the [rows][k] fp32 distances within kChunkBytes
+inline int64_t kmeans_assign_rows(int64_t n, int k) { return scratch_rows(n, (size_t)k * 4); }
+
+// queries per chunk of the stateless exact search: the [c][nb] fp32 distances within kChunkBytes
+inline int64_t flat_search_query_chunk(int64_t n, int64_t nb) {
+  return scratch_rows(n, (size_t)std::max<int64_t>(nb, 1) * 4);
+}
+
 // the calling thread's last failure, of whichever index (ivfpq_last_error)
 inline thread_local std::string g_err;
 

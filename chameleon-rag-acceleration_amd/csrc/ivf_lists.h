@@ -49,12 +49,12 @@ struct IvfLists : StreamOrder {
   virtual IvfFlatPlan plan(int k, int64_t slots) const = 0;
   // bytes per [query][list] entry of a chunk: the coarse keys and the buckets, and what the row type adds
   virtual size_t entry_bytes() const { return 8; }
+  // whether a chunk keeps its [c][np][d] residual queries (they bound the chunk: ivf_query_chunk)
+  virtual bool resid_queries() const { return false; }
   // The row type's own workspaces for chunks of at most qc queries with np probes each, before
-  // the first chunk; returns qc or a tighter bound.  zero_coarse: the probes are preassigned
-  // without their coarse values.
-  virtual int64_t prepare_chunks(int64_t qc, int np, bool zero_coarse, hipStream_t s) {
-    (void)np, (void)zero_coarse, (void)s;
-    return qc;
+  // the first chunk.  zero_coarse: the probes are preassigned without their coarse values.
+  virtual void prepare_chunks(int64_t qc, int np, bool zero_coarse, hipStream_t s) {
+    (void)qc, (void)np, (void)zero_coarse, (void)s;
   }
   // plan + scan + merge of one chunk; cdis: [f.nq][f.nprobe] coarse values of the probes (null:
   // preassigned without them)
@@ -105,13 +105,8 @@ struct IvfLists : StreamOrder {
     img_n = ntotal = next_id = 0;
   }
 
-  // rows per pass of add and train: the [rows][nlist] coarse keys within kChunkBytes, and a
-  // [rows][d] fp32 staging buffer where the pass has one
-  int64_t chunk_rows(int64_t n, bool staged) const {
-    int64_t rows = nlist >= kSegmentedNlist ? (int64_t)1 << 18 : (int64_t)(kChunkBytes / ((size_t)nlist * 4));
-    if (staged) rows = std::min<int64_t>(rows, (int64_t)(kChunkBytes / (sizeof(float) * d)));
-    return std::max<int64_t>(1, std::min(n, rows));
-  }
+  // rows per pass of add and train (ivf_pass_rows; staged: the pass has a [rows][d] fp32 staging buffer)
+  int64_t chunk_rows(int64_t n, bool staged) const { return ivf_pass_rows(n, nlist, d, staged); }
 
   // An add of n rows: room behind the pending set (reserve), then the caller writes the rows
   // and their lists there on s, then the labels (ids) and the commit.  The pending set is
@@ -167,14 +162,8 @@ struct IvfLists : StreamOrder {
     }
     const int np = Iq ? nprobe : std::min(nprobe, nlist);
     const IvfFlatPlan pl = plan(k, range_top[std::min(np, nlist)]);
-    // queries per chunk: the [c][nlist] coarse keys, buckets and what the row type keeps per
-    // entry within kChunkBytes, the partial lists (12 bytes per entry, and the first merge
-    // round's output) within kPartialBytes
-    const size_t part_q = (size_t)pl.S * k * 12 * 2;
-    int64_t qc = std::max<int64_t>(
-        1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)nlist * entry_bytes())),
-                              (int64_t)(kPartialBytes / part_q), (int64_t)(INT32_MAX / 2) / ((int64_t)pl.S * k)}));
-    qc = prepare_chunks(qc, np, Iq && !Dq, s);
+    const int64_t qc = ivf_query_chunk(n, nlist, entry_bytes(), pl.S, k, np, d, resid_queries());
+    prepare_chunks(qc, np, Iq && !Dq, s);
     if (!Iq) {
       w_lists.ensure(sizeof(int64_t) * qc * np);
       w_dis.ensure(sizeof(float) * qc * np);

@@ -143,4 +143,31 @@ int ivfpq_ivfflat_get_list(ivfpq_ivfflat_index* h, int list, float* vectors, int
   return ivf_get_list(h, list, vectors, ids);
 }
 
+// ---- how IvfLists cuts a batch (IndexIVFFlat and IndexIVFScalarQuantizer): host arithmetic ----
+int ivfpq_ivf_get_plan(int k, int64_t slots, int* S, int* fan) {
+  return guarded([&] {
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(slots >= 0 && slots < (int64_t)INT32_MAX / kIvfFlatWaves / 2, "slots out of range");
+    const IvfFlatPlan pl = ivfflat_plan(k, slots);  // (ivfsq_plan differs in G alone)
+    if (S) *S = pl.S;
+    if (fan) *fan = pl.fan;
+  });
+}
+
+int ivfpq_ivf_get_query_chunk(int64_t nq, int nlist, int entry_bytes, int S, int k, int nprobe, int d,
+                              int resid_queries, int64_t* query_chunk) {
+  return guarded([&] {
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(nq >= 0 && nlist >= 1 && entry_bytes >= 1 && S >= 1 && nprobe >= 1 && d >= 1, "shape out of range");
+    if (query_chunk) *query_chunk = ivf_query_chunk(nq, nlist, (size_t)entry_bytes, S, k, nprobe, d, resid_queries != 0);
+  });
+}
+
+int ivfpq_ivf_get_pass_rows(int64_t n, int nlist, int d, int staged, int64_t* rows) {
+  return guarded([&] {
+    require(n >= 0 && nlist >= 1 && d >= 1, "shape out of range");
+    if (rows) *rows = ivf_pass_rows(n, nlist, d, staged != 0);
+  });
+}
+
 }  // extern "C"

@@ -405,8 +405,7 @@ struct ivfpq_index {
     quiesce();
     // the pending sort permutes entries with 32-bit indices
     require(q.n + n < (int64_t(1) << 32) - 1, "more than 2^32 - 2 vectors pending in one merge");
-    const int64_t rows = nlist >= kSegmentedNlist ? std::min<int64_t>(n, 1 << 18)
-                                                  : std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / ((size_t)nlist * 4)));
+    const int64_t rows = ivf_pass_rows(n, nlist, d, false);
     q.reserve(q.n + n, s);
     int64_t* lists = q.lists.as<int64_t>() + q.n;
     w_D.ensure(sizeof(float) * rows);
@@ -617,15 +616,9 @@ struct ivfpq_index {
     mark_done(s);
   }
 
-  // The query chunk of a search: [c][nlist] keys, T3 and buckets within
-  // kChunkBytes; the per-wave partial lists ([c][np][4][k] 16-B records, 64 B per
-  // entry and query) within kPartialBytes, so large k still runs whole
-  // 1024-query batches (C3, k = 1000, nprobe 32: 2 MB per query).
+  // the query chunk of a search (ivfpq_query_chunk)
   int64_t query_chunk(int64_t n, int np, int k) const {
-    const int nloc = std::max(list_hi - list_lo, 1);
-    const size_t per_q = std::max({(size_t)nlist * 4, (size_t)M * ksub * 4, (size_t)nloc * 16});
-    return std::max<int64_t>(
-        1, std::min<int64_t>({n, (int64_t)(kChunkBytes / per_q), (int64_t)(kPartialBytes / ((size_t)np * part_stride(k) * 64))}));
+    return ivfpq_query_chunk(n, nlist, M, ksub, list_hi - list_lo, np, k);
   }
 
   // T3 [n][M][ksub] of the queries x, on stream s, ahead of a preassigned search
@@ -1327,7 +1320,7 @@ int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n,
     dbn.ensure(sizeof(float) * nbb);
     if (nb) HIPCHECK(hipMemcpyAsync(dxb.p, xb, sizeof(float) * nb * d, hipMemcpyHostToDevice, s));
     launch_row_norms(dxb.as<float>(), nb, d, dbn.as<float>(), s);
-    const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / ((size_t)nbb * 4)));
+    const int64_t qc = flat_search_query_chunk(n, nb);
     dx.ensure(sizeof(float) * qc * d);
     dxn.ensure(sizeof(float) * qc);
     ddist.ensure(sizeof(float) * qc * nbb);
@@ -1345,6 +1338,28 @@ int ivfpq_flat_search(int device, int d, int64_t nb, const float* xb, int64_t n,
       HIPCHECK(hipMemcpyAsync(I + q0 * k, dI.p, sizeof(int64_t) * c * k, hipMemcpyDeviceToHost, s));
       HIPCHECK(hipStreamSynchronize(s));
     }
+  });
+}
+
+int ivfpq_flat_search_get_query_chunk(int64_t n, int64_t nb, int64_t* query_chunk) {
+  return guarded([&] {
+    require(n >= 0 && nb >= 0, "invalid shape");
+    if (query_chunk) *query_chunk = flat_search_query_chunk(n, nb);
+  });
+}
+
+int ivfpq_get_query_chunk(int64_t nq, int nlist, int M, int nbits, int nloc, int nprobe, int k, int64_t* query_chunk) {
+  return guarded([&] {
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(nq >= 0 && nlist >= 1 && M >= 1 && nbits >= 1 && nbits <= 16 && nloc >= 0 && nprobe >= 1, "invalid shape");
+    if (query_chunk) *query_chunk = ivfpq_query_chunk(nq, nlist, M, 1 << nbits, nloc, nprobe, k);
+  });
+}
+
+int ivfpq_kmeans_get_assign_rows(int64_t n, int k, int64_t* rows) {
+  return guarded([&] {
+    require(n >= 0 && k >= 1, "invalid shape");
+    if (rows) *rows = kmeans_assign_rows(n, k);
   });
 }
 

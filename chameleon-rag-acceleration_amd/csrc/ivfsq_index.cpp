@@ -43,16 +43,14 @@ struct ivfpq_ivfsq_index : IvfLists {
   IvfFlatPlan plan(int k, int64_t slots) const override { return ivfsq_plan(codec, k, slots); }
   // the probe column of every bucket entry beside the coarse keys and buckets
   size_t entry_bytes() const override { return by_residual ? 12 : 8; }
-  // the [c][np][d] residual queries within kChunkBytes
-  int64_t prepare_chunks(int64_t qc, int np, bool zero_coarse, hipStream_t s) override {
-    if (resid_q()) qc = std::max<int64_t>(1, std::min<int64_t>(qc, (int64_t)(kChunkBytes / (sizeof(float) * np * d))));
+  bool resid_queries() const override { return resid_q(); }
+  void prepare_chunks(int64_t qc, int np, bool zero_coarse, hipStream_t s) override {
     if (coarse_add() && zero_coarse) {
       w_cd.ensure(sizeof(float) * qc * np);
       HIPCHECK(hipMemsetAsync(w_cd.p, 0, sizeof(float) * qc * np, s));
     }
     if (by_residual) p_probe.ensure(sizeof(int32_t) * (size_t)nlist * qc);
     if (resid_q()) p_qr.ensure(sizeof(float) * (size_t)qc * np * d);
-    return qc;
   }
   void launch_chunk(const IvfFlatArgs& f, const IvfFlatPlan& pl, const float* cdis, hipStream_t s) override {
     IvfSqArgs a;

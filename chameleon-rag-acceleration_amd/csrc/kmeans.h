@@ -96,7 +96,7 @@ struct KMeans {
     w_cn.ensure(sizeof(float) * k);
     HIPCHECK(hipMemcpyAsync(w_cent.p, cent, sizeof(float) * k * dd, hipMemcpyHostToDevice, stream));
     launch_row_norms(w_cent.as<float>(), k, dd, w_cn.as<float>(), stream);
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, kChunkBytes / ((size_t)k * 4)));
+    const int64_t rows = kmeans_assign_rows(n, k);
     w_xn.ensure(sizeof(float) * rows);
     w_dist.ensure(sizeof(float) * rows * k);
     w_D.ensure(sizeof(float) * rows);

@@ -111,11 +111,7 @@ struct ivfpq_sq_index : CodeStore {
       return;
     }
     const IvfFlatPlan pl = ivfflat_plan(k, sq_scan_ranges(ntotal));
-    // queries per chunk: the partial lists (12 bytes per entry, and the first merge round's
-    // output) within kPartialBytes, their count within the merge's 32-bit indexing
-    const size_t part_q = (size_t)pl.S * k * 12 * 2;
-    const int64_t qc = std::max<int64_t>(
-        1, std::min<int64_t>({n, (int64_t)(kPartialBytes / part_q), (int64_t)(INT32_MAX / 2) / ((int64_t)pl.S * k)}));
+    const int64_t qc = partial_query_chunk(n, pl.S, k);
     p_tau.ensure(sizeof(uint32_t) * qc);
     p_partD.ensure(sizeof(float) * (size_t)pl.S * qc * k);
     p_partI.ensure(sizeof(int64_t) * (size_t)pl.S * qc * k);
@@ -294,6 +290,25 @@ int ivfpq_sq_decode(ivfpq_sq_index* h, int64_t n, const uint8_t* codes, float* x
     if (n <= 0) return;
     require(x != nullptr && codes != nullptr, "null x / codes");
     h->decode_host(n, codes, x);
+  });
+}
+
+// ---- how the batches are cut: host arithmetic, no handle ----
+int ivfpq_sq_get_plan(int64_t nq, int64_t nb, int k, int* S, int* fan, int64_t* query_chunk) {
+  return guarded([&] {
+    require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
+    require(nb >= 0 && nb < (int64_t)INT32_MAX && nq >= 0, "nb / nq out of range");
+    const IvfFlatPlan pl = ivfflat_plan(k, sq_scan_ranges(nb));
+    if (S) *S = pl.S;
+    if (fan) *fan = pl.fan;
+    if (query_chunk) *query_chunk = partial_query_chunk(nq, pl.S, k);
+  });
+}
+
+int ivfpq_host_get_pass_rows(int64_t n, int64_t in_bytes, int64_t* rows) {
+  return guarded([&] {
+    require(n >= 0 && in_bytes >= 1, "shape out of range");
+    if (rows) *rows = CodeStore::host_rows(n, (size_t)in_bytes);
   });
 }
 

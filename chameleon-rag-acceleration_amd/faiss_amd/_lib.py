@@ -227,6 +227,17 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_int), c_i64p, ctypes.POINTER(ctypes.c_int),
                                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                  ctypes.POINTER(ctypes.c_int), c_i64p]),
+    # how the host cuts a batch into chunks (host arithmetic; faiss_amd.index.*_split)
+    "ivfpq_ivf_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int)]),
+    "ivfpq_ivf_get_query_chunk": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 7 + [c_i64p]),
+    "ivfpq_ivf_get_pass_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64p]),
+    "ivfpq_sq_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int), c_i64p]),
+    "ivfpq_get_query_chunk": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 6 + [c_i64p]),
+    "ivfpq_host_get_pass_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_i64p]),
+    "ivfpq_flat_search_get_query_chunk": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_i64p]),
+    "ivfpq_kmeans_get_assign_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_i64p]),
 }
 
 

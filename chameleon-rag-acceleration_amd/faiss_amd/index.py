@@ -289,6 +289,59 @@ def flat_search_plan(nq, nb, k, range_rows=0):
     return out
 
 
+# How the host cuts a batch into chunks ("Host-side splits"): each function returns
+# what the library's own loop computes (host arithmetic, no device); the tests assert their cuts
+# from these.
+def _i64_from(name, *args):
+    out = ctypes.c_int64()
+    _lib.check(getattr(_lib.load(), name)(*[int(a) for a in args], ctypes.byref(out)))
+    return out.value
+
+
+def ivf_search_split(nq, nlist, k, nprobe, d, slots, entry_bytes=8, resid_queries=False):
+    """An IndexIVFFlat / IndexIVFScalarQuantizer search of nq queries whose probed lists hold at
+    most ``slots`` row ranges (ivfpq_ivf_get_plan, ivfpq_ivf_get_query_chunk): dict of S, fan,
+    query_chunk.  entry_bytes is 12 and resid_queries true as the C header says."""
+    S, fan = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().ivfpq_ivf_get_plan(int(k), int(slots), ctypes.byref(S), ctypes.byref(fan)))
+    qc = _i64_from("ivfpq_ivf_get_query_chunk", nq, nlist, entry_bytes, S.value, k, nprobe, d, bool(resid_queries))
+    return dict(S=S.value, fan=fan.value, query_chunk=qc)
+
+
+def ivf_pass_rows(n, nlist, d, staged=False):
+    """Rows per pass of an IVF add or scalar-quantizer training pass (ivfpq_ivf_get_pass_rows)."""
+    return _i64_from("ivfpq_ivf_get_pass_rows", n, nlist, d, bool(staged))
+
+
+def sq_search_plan(nq, nb, k):
+    """An IndexScalarQuantizer search (ivfpq_sq_get_plan): dict of S, fan, query_chunk."""
+    S, fan, qc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _lib.check(_lib.load().ivfpq_sq_get_plan(int(nq), int(nb), int(k), ctypes.byref(S), ctypes.byref(fan),
+                                             ctypes.byref(qc)))
+    return dict(S=S.value, fan=fan.value, query_chunk=qc.value)
+
+
+def ivfpq_query_chunk(nq, nlist, M, nprobe, k, nbits=8, nloc=None):
+    """Queries per chunk of an IndexIVFPQ search (ivfpq_get_query_chunk); nloc: the lists a
+    list-range shard holds (default: all)."""
+    return _i64_from("ivfpq_get_query_chunk", nq, nlist, M, nbits, nlist if nloc is None else nloc, nprobe, k)
+
+
+def host_pass_rows(n, in_bytes):
+    """Rows per pass of n host rows through a flat index's staging buffer (ivfpq_host_get_pass_rows)."""
+    return _i64_from("ivfpq_host_get_pass_rows", n, in_bytes)
+
+
+def flat_search_query_chunk(n, nb):
+    """Queries per chunk of the stateless exact search (ivfpq_flat_search_get_query_chunk)."""
+    return _i64_from("ivfpq_flat_search_get_query_chunk", n, nb)
+
+
+def kmeans_assign_rows(n, k):
+    """Rows per pass of a k-means assignment to k centroids (ivfpq_kmeans_get_assign_rows)."""
+    return _i64_from("ivfpq_kmeans_get_assign_rows", n, k)
+
+
 class IndexFlatL2(IndexFlat):
     """faiss.IndexFlatL2(d): IndexFlat with the L2 metric (the default coarse quantizer)."""
 

@@ -560,6 +560,40 @@ int ivfpq_flat_index_set_range_rows(ivfpq_flat_index* h, int64_t rows);
 int ivfpq_flat_index_get_plan(int64_t nq, int64_t nb, int k, int64_t set_rows, int* tile_q, int64_t* range_rows,
                               int* ranges, int* S, int* fan, int* rounds, int64_t* query_chunk);
 
+/* ------------------------------------------------------------------------------------------
+ * How the host cuts a batch into chunks ("Host-side splits").  Each getter returns
+ * what the loop it names computes, from the same function: host arithmetic only, no handle, no
+ * device call, outputs nullable.  The test suite uses them to assert that a batch is cut.
+ * ------------------------------------------------------------------------------------------ */
+/* The list scans of IndexIVFFlat and IndexIVFScalarQuantizer: S = the sorted partial lists per
+ * query for k results when a query's probed lists hold at most `slots` row ranges of 4096 rows,
+ * merged `fan` at a time. */
+int ivfpq_ivf_get_plan(int k, int64_t slots, int* S, int* fan);
+/* ... and the queries per chunk of their searches: nq, the [chunk][nlist] entries of entry_bytes
+ * each (8; 12 for IndexIVFScalarQuantizer by_residual) within 256 MiB, the partial lists
+ * (S * k * 24 bytes per query) within 2 GiB, and where residual queries are kept (by_residual with
+ * L2) their [chunk][nprobe][d] floats within 256 MiB. */
+int ivfpq_ivf_get_query_chunk(int64_t nq, int nlist, int entry_bytes, int S, int k, int nprobe, int d,
+                              int resid_queries, int64_t* query_chunk);
+/* The rows per pass of their adds, of IVF-PQ's, and of the scalar quantizer's training pass: the
+ * [rows][nlist] coarse keys within 256 MiB (2^18 rows from nlist 8192 on), and where the pass
+ * stages its rows (IndexIVFScalarQuantizer) their [rows][d] floats within 256 MiB. */
+int ivfpq_ivf_get_pass_rows(int64_t n, int nlist, int d, int staged, int64_t* rows);
+/* IndexScalarQuantizer's search of nq queries over nb codes: S, fan as above with
+ * slots = ceil(nb / 4096), and the queries per chunk. */
+int ivfpq_sq_get_plan(int64_t nq, int64_t nb, int k, int* S, int* fan, int64_t* query_chunk);
+/* The rows per pass of n host rows of in_bytes each through a flat index's staging buffer
+ * (add, sa_encode, sa_decode, the scalar quantizer's training). */
+int ivfpq_host_get_pass_rows(int64_t n, int64_t in_bytes, int64_t* rows);
+/* The queries per chunk of an IVF-PQ search (ivfpq_search and its kin) of a handle that holds
+ * nloc of the nlist lists: the keys, the M * 2^nbits table entries and the buckets of a query
+ * within 256 MiB, its nprobe * k * 64 bytes of partial lists within 2 GiB. */
+int ivfpq_get_query_chunk(int64_t nq, int nlist, int M, int nbits, int nloc, int nprobe, int k, int64_t* query_chunk);
+/* The queries per chunk of ivfpq_flat_search over nb rows. */
+int ivfpq_flat_search_get_query_chunk(int64_t n, int64_t nb, int64_t* query_chunk);
+/* The rows per pass of a k-means assignment to k centroids (every *_train). */
+int ivfpq_kmeans_get_assign_rows(int64_t n, int k, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

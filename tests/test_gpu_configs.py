@@ -518,3 +518,68 @@ def test_shard_step_pipelined_on_two_streams(sift1m):
         assert_same(D.cpu().numpy(), I.cpu().numpy(), ref[b][0][r * B:(r + 1) * B], ref[b][1][r * B:(r + 1) * B])
     for sh in shards:
         assert sh.error_count() == 0 and sh.repair_stats() == (0, 0)
+
+
+# (d, nlist, M, metric, nprobe, slice queries or None for two coarse chunks and a short one)
+FRONT_HALF = {
+    "tiled": (768, 1500, 64, faiss.METRIC_INNER_PRODUCT, 32, 129),
+    "segmented": (96, 20000, 48, faiss.METRIC_L2, 32, 17),
+    "coarse_chunks": (32, 8191, 8, faiss.METRIC_L2, 16, None),
+}
+
+
+@pytest.mark.parametrize("path", list(FRONT_HALF))
+def test_shard_front_half_on_every_coarse_path(path):
+    """coarse_tables_device beyond the small-nlist GEMM, where the tables are extra
+    workgroups of k_coarse_gemm: on the tiled coarse path (d >= 256, 1024 < nlist < 8192),
+    on the segmented one (nlist >= 8192, the tables a launch of their own) and with a slice
+    that the host cuts into several coarse chunks, only the first of which builds the tables
+    (the [chunk][nlist] fp32 keys within kChunkBytes: 8193 queries at nlist = 8191, so 16393
+    are two full chunks and a short one).  The tables are those of 200 other queries.  The
+    coarse half equals coarse_device of the slice; the preassigned search that consumes the
+    token equals the one without a token and the oracle."""
+    import torch
+
+    from faiss_amd import index as fidx
+
+    d, nlist, M, metric, nprobe, ns = FRONT_HALF[path]
+    rng = np.random.default_rng(sorted(FRONT_HALF).index(path) + 40)
+    if ns is None:
+        chunk = fidx.ivf_pass_rows(10 ** 6, nlist, d, False)  # the same [rows][nlist] fp32 keys
+        assert chunk == (256 << 20) // (4 * nlist) == 8193
+        ns = 2 * chunk + 7
+        assert ns == 16393
+    cent = rng.standard_normal((nlist, d), dtype=np.float32)
+    cb = (0.5 * rng.standard_normal((M, 256, d // M), dtype=np.float32))
+    ix = faiss.IndexIVFPQ(None, d, nlist, M, 8, metric, device=0)
+    ix.set_trained(cent, cb)
+    ix.nprobe = nprobe
+    xt = rng.standard_normal((200, d), dtype=np.float32)
+    xs = xt[:ns] if ns <= len(xt) else rng.standard_normal((ns, d), dtype=np.float32)
+    xtd, xsd = torch.from_numpy(xt).cuda(), torch.from_numpy(xs).contiguous().cuda()
+    Dt, It = ix.coarse_device(xtd)
+    # 20000 codes in the lists the 200 queries probe
+    lists = np.unique(It.cpu().numpy())
+    nb = 20000
+    list_no = rng.choice(lists, nb).astype(np.int64)
+    codes = rng.integers(0, 256, size=(nb, M), dtype=np.uint8)
+    ids = rng.permutation(3 * nb)[:nb].astype(np.int64)
+    ix.add_preencoded(list_no, codes, ids)
+    ox = O.OracleIVFPQ(d, nlist, M, metric=metric)
+    ox.set_trained(cent, cb)
+    ox.add_preencoded(list_no, codes, ids)
+
+    Dc, Ic = ix.coarse_device(xsd)
+    Dq, Iq, tok = ix.coarse_tables_device(xsd, xtd)
+    torch.cuda.synchronize()
+    assert Iq.shape == (ns, nprobe)
+    assert torch.equal(Iq, Ic) and torch.equal(Dq, Dc)
+    k = 10
+    D, I = ix.search_preassigned_device(xtd, k, It, Dt, tables=tok)
+    D0, I0 = ix.search_preassigned_device(xtd, k, It, Dt)
+    torch.cuda.synchronize()
+    assert torch.equal(I, I0) and torch.equal(D, D0)
+    Dr, Ir = ox.search_preassigned(xt, k, It.cpu().numpy(), Dt.cpu().numpy())
+    assert_same(D.cpu().numpy(), I.cpu().numpy(), Dr, Ir)
+    assert (Ir >= 0).all()
+    assert ix.error_count() == 0

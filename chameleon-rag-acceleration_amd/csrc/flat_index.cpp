@@ -11,25 +11,6 @@
 
 using namespace chivf;
 
-namespace {
-
-// the queries of one launch and its plan: the partial lists (12 bytes per entry, and the first
-// merge round's output) within kPartialBytes, their count within the merge's 32-bit indexing
-int64_t flat_query_chunk(int64_t n, int64_t nb, int k, int64_t force, FlatScanPlan* out) {
-  int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, 1 << 16));
-  FlatScanPlan pl = flat_scan_plan(qc, nb, k, force);
-  while (true) {
-    const int64_t lim = partial_list_queries(pl.S, k);
-    if (qc <= lim) break;
-    qc = std::max<int64_t>(1, std::min(lim, qc / 2));
-    pl = flat_scan_plan(qc, nb, k, force);  // fewer query tiles: more ranges
-  }
-  if (out) *out = pl;
-  return qc;
-}
-
-}  // namespace
-
 struct ivfpq_flat_index : CodeStore {
   int d = 0, metric = IVFPQ_METRIC_L2;
   DevBuf d_norms;              // [cap] |y|^2 of the image's rows

@@ -11,6 +11,7 @@
 #include <string>
 #include <utility>
 
+#include "flat_scan.h"      // FlatScanPlan
 #include "ivfpq_kernels.h"  // kMaxK
 
 namespace chivf {
@@ -88,6 +89,22 @@ inline int64_t partial_list_queries(int S, int k) {
   const size_t part_q = (size_t)S * k * 12 * 2;
   return std::max<int64_t>(
       1, std::min<int64_t>((int64_t)(kPartialBytes / part_q), (int64_t)(INT32_MAX / 2) / ((int64_t)S * k)));
+}
+
+// the queries of one launch of the flat index's fused scan (IndexFlat's searches, the k-means
+// assignment at k = 1) and its plan: the partial lists within kPartialBytes, their count
+// within the merge's 32-bit indexing
+inline int64_t flat_query_chunk(int64_t n, int64_t nb, int k, int64_t force, FlatScanPlan* out) {
+  int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, 1 << 16));
+  FlatScanPlan pl = flat_scan_plan(qc, nb, k, force);
+  while (true) {
+    const int64_t lim = partial_list_queries(pl.S, k);
+    if (qc <= lim) break;
+    qc = std::max<int64_t>(1, std::min(lim, qc / 2));
+    pl = flat_scan_plan(qc, nb, k, force);  // fewer query tiles: more ranges
+  }
+  if (out) *out = pl;
+  return qc;
 }
 
 // queries per chunk of a search whose scan leaves S partial lists per query (IndexScalarQuantizer)

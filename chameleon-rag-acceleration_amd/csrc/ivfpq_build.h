@@ -30,6 +30,10 @@ hipError_t image_merge_sort(const ImageMergeArgs& g, void* scratch, size_t scrat
 // phase 2: the first n_out sorted entries' codes and labels into codes_out / ids_out
 hipError_t image_merge_gather(const ImageMergeArgs& g, int64_t n_out, void* scratch, hipStream_t s);
 void launch_iota_i64(int64_t* v, int64_t n, int64_t start, hipStream_t s);
+// bits of a radix sort whose keys are list numbers in [0, nlist]
+int key_bits(int nlist);
+// off[l] = first position of sorted [n] (ascending list numbers) whose list is >= l, for l in [0, nlist]
+void launch_list_offsets(const uint32_t* sorted, int64_t n, int nlist, int64_t* off, hipStream_t s);
 
 // Per-list merge of a new image (new_off / new_codes / new_ids: entries sorted by
 // (list, label), e.g. the output of image_merge_sort + image_merge_gather over the

@@ -97,13 +97,17 @@ __global__ __launch_bounds__(256) void k_gather_entries(const uint32_t* __restri
   ids[i] = ids_all[src];
 }
 
+}  // namespace
+
 int key_bits(int nlist) {
   int b = 1;
   while ((1ll << b) <= (int64_t)nlist) b++;
   return b;
 }
 
-}  // namespace
+void launch_list_offsets(const uint32_t* sorted, int64_t n, int nlist, int64_t* off, hipStream_t s) {
+  hipLaunchKernelGGL(k_list_offsets, dim3(nblk(n + 1, 256)), dim3(256), 0, s, sorted, n, nlist, off);
+}
 
 size_t image_merge_scratch_bytes(int64_t n_all, int nlist) {
   // lno (2 x u32), perm (2 x u32), ids_all (i64), sort temp (the larger of the two sorts)
@@ -154,7 +158,7 @@ hipError_t image_merge_sort(const ImageMergeArgs& g, void* scratch, size_t scrat
   e = rocprim::radix_sort_pairs(tmp, tmp_bytes, lno2, lno, perm2, perm, (size_t)n, 0, key_bits(g.nlist), s);
   if (e != hipSuccess) return e;
   // lno: sorted lists; perm: source of every sorted position
-  hipLaunchKernelGGL(k_list_offsets, dim3(nblk(n + 1, 256)), dim3(256), 0, s, lno, n, g.nlist, g.off_out);
+  launch_list_offsets(lno, n, g.nlist, g.off_out, s);
   return hipGetLastError();
 }
 

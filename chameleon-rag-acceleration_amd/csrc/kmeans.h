@@ -45,22 +45,15 @@ inline void renorm_rows(float* x, int64_t n, int d) {
   }
 }
 
-inline void kmeans_update(const float* x, int64_t n, int d, int k, const int64_t* assign, float* cent) {
-  std::vector<double> sum((size_t)k * d, 0.0);
-  std::vector<int64_t> cnt(k, 0);
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t c = assign[i];
-    cnt[c]++;
-    double* s = &sum[(size_t)c * d];
-    const float* xi = x + i * d;
-    for (int t = 0; t < d; t++) s[t] += (double)xi[t];
-  }
-  for (int c = 0; c < k; c++)
-    if (cnt[c] > 0)
-      for (int t = 0; t < d; t++) cent[(size_t)c * d + t] = (float)(sum[(size_t)c * d + t] / (double)cnt[c]);
+// The second loop of a k-means update (Faiss split_clusters' rule, the oracle's order): every
+// empty cluster, in ascending order, takes the largest cluster's centroid, the two perturbed
+// by +-1/1024 in alternating dimensions, and half its count.  Returns the clusters split.
+inline int64_t kmeans_split_empty(float* cent, int64_t* cnt, int k, int d) {
   const float eps = 1.0f / 1024.0f;
+  int64_t nsplit = 0;
   for (int c = 0; c < k; c++) {
     if (cnt[c] != 0) continue;
+    nsplit++;
     int big = 0;
     for (int j = 1; j < k; j++)
       if (cnt[j] > cnt[big]) big = j;
@@ -77,6 +70,23 @@ inline void kmeans_update(const float* x, int64_t n, int d, int k, const int64_t
     cnt[c] = cnt[big] / 2;
     cnt[big] -= cnt[c];
   }
+  return nsplit;
+}
+
+inline void kmeans_update(const float* x, int64_t n, int d, int k, const int64_t* assign, float* cent) {
+  std::vector<double> sum((size_t)k * d, 0.0);
+  std::vector<int64_t> cnt(k, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t c = assign[i];
+    cnt[c]++;
+    double* s = &sum[(size_t)c * d];
+    const float* xi = x + i * d;
+    for (int t = 0; t < d; t++) s[t] += (double)xi[t];
+  }
+  for (int c = 0; c < k; c++)
+    if (cnt[c] > 0)
+      for (int t = 0; t < d; t++) cent[(size_t)c * d + t] = (float)(sum[(size_t)c * d + t] / (double)cnt[c]);
+  kmeans_split_empty(cent, cnt.data(), k, d);
 }
 
 // One training run's scratch, on the stream it is given; made and released by the

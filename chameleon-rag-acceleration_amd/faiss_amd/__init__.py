@@ -35,6 +35,12 @@ from .index import (  # noqa: F401
     write_index,
     write_index_binary,
 )
+from .clustering import (  # noqa: F401
+    Clustering,
+    Kmeans,
+    normalize_L2,
+    vector_float_to_array,
+)
 from .transform import (  # noqa: F401
     IndexPreTransform,
     LinearTransform,

@@ -227,6 +227,19 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_int), c_i64p, ctypes.POINTER(ctypes.c_int),
                                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                  ctypes.POINTER(ctypes.c_int), c_i64p]),
+    # stand-alone k-means (Kmeans / Clustering)
+    "ivfpq_clus_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(c_handle)]),
+    "ivfpq_clus_free": (ctypes.c_int, [c_handle]),
+    "ivfpq_clus_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_uint64, c_f32p]),
+    "ivfpq_clus_train_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
+    "ivfpq_clus_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
+    "ivfpq_clus_get_stats": (ctypes.c_int, [c_handle, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_double), c_i64p]),
+    "ivfpq_clus_set_pass_rows": (ctypes.c_int, [c_handle, ctypes.c_int64]),
+    "ivfpq_clus_rand_perm_prefix": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, c_i64p]),
     # how the host cuts a batch into chunks (host arithmetic; faiss_amd.index.*_split)
     "ivfpq_ivf_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]),

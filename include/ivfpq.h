@@ -561,6 +561,49 @@ int ivfpq_flat_index_get_plan(int64_t nq, int64_t nb, int k, int64_t set_rows, i
                               int* ranges, int* S, int* fan, int* rounds, int64_t* query_chunk);
 
 /* ------------------------------------------------------------------------------------------
+ * Stand-alone k-means (faiss.Kmeans / faiss.Clustering: bench_gpu_1bn.py:522-542
+ * train_coarse_quantizer, wav2vec_cluster_faiss.py:186-203).  Lloyd iterations resident on the
+ * GPU: the assignment is the flat index's fused scan at k = 1 over the centroids (first best
+ * wins on ties, no distance matrix), the update adds every cluster's rows in ascending row
+ * order into one fp64 chain per (cluster, dimension) -- the order of every *_train's host
+ * update, so the centroids are those of oracle.kmeans bit for bit -- and the objective of an
+ * iteration is the fp64 sum of its assignment's keys, reduced in a fixed order.  No
+ * floating-point atomics: two runs give the same bits.  Supported pairs: L2 with
+ * spherical = 0, inner product with spherical = 1 (centroids renormalised after every
+ * update); create rejects any other pair and bad shapes before any device call.  Same
+ * conventions, errors and locking as above.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ivfpq_clus ivfpq_clus;
+
+int ivfpq_clus_create(int d, int k, int metric, int spherical, int device, ivfpq_clus** out);
+int ivfpq_clus_free(ivfpq_clus* h); /* free(NULL) returns 0 */
+/* nredo runs of niter iterations over the host rows x [n][d]; run r starts from the rows
+ * rand_perm_prefix(n, k, seed + 15486557 r), or every run from init [k][d] (host) when it is
+ * not NULL.  The run with the best final objective is kept (smallest for L2, largest for inner
+ * product; ties keep the earlier run).  The rows stay in HBM across iterations when they fit
+ * 8 GiB, and are streamed pass by pass in every iteration otherwise.  n >= k; niter >= 0;
+ * nredo >= 1 (checked before the handle). */
+int ivfpq_clus_train(ivfpq_clus* h, int64_t n, const float* x, int niter, int nredo, uint64_t seed,
+                     const float* init);
+/* The same with x in HBM, all device work on `stream` (hipStream_t, NULL = default); init is a
+ * host pointer.  Returns when the training is complete. */
+int ivfpq_clus_train_device(ivfpq_clus* h, int64_t n, const float* x, int niter, int nredo, uint64_t seed,
+                            const float* init, void* stream);
+int ivfpq_clus_get_centroids(ivfpq_clus* h, float* out); /* [k][d] of the kept run */
+/* The kept run (outputs nullable): its iterations, obj [niter] = every iteration's objective
+ * (Faiss iteration_stats[it].obj, taken before the update), nsplit [niter] = the empty clusters
+ * split in that iteration's update. */
+int ivfpq_clus_get_stats(ivfpq_clus* h, int* niter, double* obj, int64_t* nsplit);
+/* The rows of one pass (assignment, ordering, accumulation): 0 (default) = chosen per call;
+ * rows > 0 forces passes of that many rows and, for host rows, the streamed path.  Results do
+ * not depend on it (the passes continue the same chains); the test suite uses it to reach
+ * several passes with small inputs, as ivfpq_flat_index_set_range_rows above. */
+int ivfpq_clus_set_pass_rows(ivfpq_clus* h, int64_t rows);
+/* The library's generator: the first k entries of a seeded random permutation of [0, n)
+ * (initial centroids, and the rows Kmeans / Clustering subsample).  No device call. */
+int ivfpq_clus_rand_perm_prefix(int64_t n, int64_t k, uint64_t seed, int64_t* out);
+
+/* ------------------------------------------------------------------------------------------
  * How the host cuts a batch into chunks ("Host-side splits").  Each getter returns
  * what the loop it names computes, from the same function: host arithmetic only, no handle, no
  * device call, outputs nullable.  The test suite uses them to assert that a batch is cut.

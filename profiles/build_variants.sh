@@ -5,11 +5,14 @@
 #   fourpass  -DSCAN_LEAN_PASSES=4  (four-pass k_scan_lean, profiles/scan_four_pass.md)
 #   onepass   -DSCAN_LEAN_SPLIT=0   (one-pass k_scan_lean, profiles/scan_split_lut.md)
 #   nofill    -DPLAN_FILL_LEAD=0    (work items of one kind only, profiles/plan_fill_lead.md)
+#   noitembound -DSCAN_ITEM_BOUND=0 (tau_q from the per-wave k-th keys only, profiles/scan_item_bound.md)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/chameleon-rag-acceleration_amd/csrc
+L=$R/chameleon-rag-acceleration_amd/lib
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I$R/include -I$C"
-[ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0" "nofill:-DPLAN_FILL_LEAD=0"
+[ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0" "nofill:-DPLAN_FILL_LEAD=0" \
+  "noitembound:-DSCAN_ITEM_BOUND=0"
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   O=$R/chameleon-rag-acceleration_amd/lib/var/$name
@@ -19,7 +22,9 @@ for spec in "$@"; do
   /opt/rocm/bin/hipcc $F $defs -c -o "$O/b.o" "$C/ivfpq_build.hip" &
   /opt/rocm/bin/hipcc $F $defs -c -o "$O/p.o" "$C/pq_flat.hip" &
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$O/libivfpq.so" "$O/k.o" "$O/b.o" "$O/p.o" "$O/i.o"
+  # the other indexes' objects do not depend on the switches: the default build's (run make first)
+  rest=$(ls "$L"/*.o | grep -v -e /ivfpq_kernels.o -e /ivfpq_index.o -e /ivfpq_build.o -e /pq_flat.o)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$O/libivfpq.so" "$O/k.o" "$O/b.o" "$O/p.o" "$O/i.o" $rest
   rm -f "$O/k.o" "$O/i.o" "$O/b.o" "$O/p.o"
   echo "built $name ($defs)"
 done

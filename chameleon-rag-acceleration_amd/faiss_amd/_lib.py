@@ -24,233 +24,134 @@ c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_handle = ctypes.c_void_p
 
+_int, _i64, _u64, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
+_intp, _u64p, _f64p = ctypes.POINTER(_int), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double)
+_new = ctypes.POINTER(c_handle)
+
+
+def _rc(*argtypes):
+    """(restype, argtypes) of a function that returns the status code."""
+    return (_int, list(argtypes))
+
+
+def _create(n):
+    return _rc(*[_int] * n, _new)
+
+
+def _dims(n):
+    return _rc(c_handle, *[_intp] * n)
+
+
+# The argument lists that more than one index family declares (include/ivfpq.h).
+HANDLE = _rc(c_handle)                                   # free, reset, is_trained, get_nprobe
+NTOTAL = (_i64, [c_handle])
+SET_INT = _rc(c_handle, _int)                            # set_nprobe and the other switches
+SET_I64 = _rc(c_handle, _i64)
+F32_ROWS = _rc(c_handle, _i64, c_f32p)                   # add without ids
+U8_ROWS = _rc(c_handle, _i64, c_u8p)                     # add_codes
+ADD_IDS = _rc(c_handle, _i64, c_f32p, c_i64p)            # add of an IVF family: ids or NULL
+ADD_DEVICE = _rc(c_handle, _i64, _vp, _vp)
+ADD_DEVICE_IDS = _rc(c_handle, _i64, _vp, _vp, _vp)
+ADD_LISTED = _rc(c_handle, _i64, c_i64p, c_u8p, c_i64p)  # codes with their list numbers and ids
+TRAIN = _rc(c_handle, _i64, c_f32p, _int, _u64)          # rows, iterations, seed
+SEARCH = _rc(c_handle, _i64, c_f32p, _int, c_f32p, c_i64p)
+SEARCH_DEVICE = _rc(c_handle, _i64, _vp, _int, _vp, _vp, _vp)
+SEARCH_PREASSIGNED = _rc(c_handle, _i64, c_f32p, _int, c_i64p, c_f32p, c_f32p, c_i64p)
+SEARCH_PREASSIGNED_DEVICE = _rc(c_handle, _i64, _vp, _int, _vp, _vp, _vp, _vp, _vp)
+F32_ARRAY = _rc(c_handle, c_f32p)                        # get_centroids, get_codebook, a one-table set_trained
+I64_ARRAY = _rc(c_handle, c_i64p)                        # get_list_sizes
+GET_TRAINED = _rc(c_handle, c_f32p, c_i64p)
+GET_CODES = _rc(c_handle, _i64, _i64, c_u8p)
+QUERY_CHUNK = _rc(_i64, _i64, c_i64p)
+
+
+def _family(prefix, **own):
+    """The signatures of one index family: what all seven have, then its own (which may replace one)."""
+    every = dict(free=HANDLE, reset=HANDLE, ntotal=NTOTAL, search=SEARCH, search_device=SEARCH_DEVICE)
+    return {prefix + name: sig for name, sig in {**every, **own}.items()}
+
+
+def _ivf(list_row):
+    """What the three IVF families add to _family's; list_row: the pointer type of a list's rows."""
+    return dict(is_trained=HANDLE, add=ADD_IDS, add_device=ADD_DEVICE_IDS, set_nprobe=SET_INT, get_nprobe=HANDLE,
+                search_preassigned=SEARCH_PREASSIGNED, search_preassigned_device=SEARCH_PREASSIGNED_DEVICE,
+                get_centroids=F32_ARRAY, get_list_sizes=I64_ARRAY, get_list=_rc(c_handle, _int, list_row, c_i64p))
+
+
 # name -> (restype, argtypes); mirrors include/ivfpq.h one to one, plus the
 # test hooks of include/ivfpq_test.h (used only by tests/).
 SIGNATURES = {
     "ivfpq_last_error": (ctypes.c_char_p, []),
-    "ivfpq_device_count": (ctypes.c_int, []),
-    "ivfpq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                    ctypes.c_int, ctypes.POINTER(c_handle)]),
-    "ivfpq_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64]),
-    "ivfpq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_i64p]),
-    "ivfpq_precompute_tables_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.POINTER(ctypes.c_uint64)]),
-    "ivfpq_search_preassigned_tables_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
-    "ivfpq_set_inflight": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_get_inflight": (ctypes.c_int, [c_handle]),
-    "ivfpq_overlap_built": (ctypes.c_int, []),
-    "ivfpq_get_error_count": (ctypes.c_int, [c_handle, c_i64p]),
-    "ivfpq_get_repair_stats": (ctypes.c_int, [c_handle, c_i64p, c_i64p]),
-    "ivfpq_get_repair_log": (ctypes.c_int, [c_handle, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
-                                            ctypes.POINTER(ctypes.c_int)]),
-    "ivfpq_set_fault_injection": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_debug_workspace": (ctypes.c_int, [c_handle, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
-                                             c_i64p]),
-    "ivfpq_debug_seed_tau": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p]),
-    "ivfpq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p]),
-    "ivfpq_add_preencoded": (ctypes.c_int, [c_handle, ctypes.c_int64, c_i64p, c_u8p, c_i64p]),
-    "ivfpq_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_set_nprobe": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_get_nprobe": (ctypes.c_int, [c_handle]),
-    "ivfpq_set_list_range": (ctypes.c_int, [c_handle, ctypes.c_int, ctypes.c_int]),
-    "ivfpq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_search_preassigned": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_i64p, c_f32p,
-                                                c_f32p, c_i64p]),
-    "ivfpq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_search_preassigned_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_serve_request": (ctypes.c_int, [c_handle, c_u8p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, c_u8p, ctypes.c_int64, c_i64p]),
-    "ivfpq_coarse_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_coarse_tables_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.POINTER(ctypes.c_uint64)]),
-    "ivfpq_merge_topk_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p]),
-    "ivfpq_linear_transform_device": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_void_p]),
+    "ivfpq_device_count": _rc(),
+    "ivfpq_overlap_built": _rc(),
+    "ivfpq_load": _rc(ctypes.c_char_p, _int, _new),
+    "ivfpq_flat_search": _rc(_int, _int, _i64, c_f32p, _i64, c_f32p, _int, _int, c_f32p, c_i64p),
+    "ivfpq_merge_topk_device": _rc(_int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp),
+    "ivfpq_linear_transform_device": _rc(_i64, _int, _int, _vp, _vp, _vp, _vp, _vp),
     # PCA training moments (PCAMatrix.train), their chunk setting and plan
-    "ivfpq_pca_moments_device": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_pca_set_chunk_rows": (ctypes.c_int, [ctypes.c_int64]),
-    "ivfpq_pca_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), c_i64p,
-                                          ctypes.POINTER(ctypes.c_int)]),
-    "ivfpq_set_timing": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_get_timing": (ctypes.c_int, [c_handle, ctypes.POINTER(ctypes.c_double), c_i64p]),
-    "ivfpq_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_is_trained": (ctypes.c_int, [c_handle]),
-    "ivfpq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 5),
-    "ivfpq_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_get_codebook": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_set_trained": (ctypes.c_int, [c_handle, c_f32p, c_f32p]),
-    "ivfpq_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
-    "ivfpq_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_u8p, c_i64p]),
-    "ivfpq_get_precomputed_table": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_save": (ctypes.c_int, [c_handle, ctypes.c_char_p]),
-    "ivfpq_load": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(c_handle)]),
-    "ivfpq_flat_search": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int64,
-                                         c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, c_i64p]),
+    "ivfpq_pca_moments_device": _rc(_i64, _int, _vp, _vp, _vp, _vp),
+    "ivfpq_pca_set_chunk_rows": _rc(_i64),
+    "ivfpq_pca_get_plan": _rc(_i64, _int, _intp, c_i64p, _intp),
+    # IVF-PQ (IndexIVFPQ)
+    **_family(
+        "ivfpq_", **_ivf(c_u8p), create=_create(6), get_dims=_dims(5),
+        train=_rc(c_handle, _i64, c_f32p, _int, _int, _u64), set_trained=_rc(c_handle, c_f32p, c_f32p),
+        add_preencoded=ADD_LISTED, set_list_range=_rc(c_handle, _int, _int),
+        get_codebook=F32_ARRAY, get_precomputed_table=F32_ARRAY, save=_rc(c_handle, ctypes.c_char_p),
+        precompute_tables_device=_rc(c_handle, _i64, _vp, _vp, _u64p),
+        search_preassigned_tables_device=_rc(c_handle, _i64, _vp, _int, _vp, _vp, _vp, _vp, _u64, _vp),
+        coarse_device=_rc(c_handle, _i64, _vp, _vp, _vp, _vp),
+        coarse_tables_device=_rc(c_handle, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _u64p),
+        serve_request=_rc(c_handle, c_u8p, _i64, _int, _int, _int, _int, c_u8p, _i64, c_i64p),
+        set_inflight=SET_INT, get_inflight=HANDLE, set_timing=SET_INT, get_timing=_rc(c_handle, _f64p, c_i64p),
+        get_error_count=I64_ARRAY, get_repair_stats=_rc(c_handle, c_i64p, c_i64p),
+        get_repair_log=_rc(c_handle, ctypes.POINTER(ctypes.c_uint32), _int, _intp), set_fault_injection=SET_INT,
+        debug_workspace=_rc(c_handle, _int, _int, _vp, _i64, c_i64p), debug_seed_tau=_rc(c_handle, _i64, _vp)),
     # flat product quantizer (IndexPQ)
-    "ivfpq_pq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(c_handle)]),
-    "ivfpq_pq_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_pq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
-    "ivfpq_pq_set_trained": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_pq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
-    "ivfpq_pq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_pq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
-    "ivfpq_pq_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_pq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_pq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_pq_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_pq_is_trained": (ctypes.c_int, [c_handle]),
-    "ivfpq_pq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 4),
-    "ivfpq_pq_get_codebook": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_pq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
-    "ivfpq_pq_debug_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), c_i64p,
-                                           ctypes.POINTER(ctypes.c_int), c_i64p]),
+    **_family(
+        "ivfpq_pq_", create=_create(5), get_dims=_dims(4), is_trained=HANDLE, train=TRAIN, set_trained=F32_ARRAY,
+        add=F32_ROWS, add_device=ADD_DEVICE, add_codes=U8_ROWS, get_codebook=F32_ARRAY, get_codes=GET_CODES,
+        debug_plan=_rc(_int, _int, _i64, _i64, _intp, _intp, c_i64p, _intp, c_i64p)),
     # IVF over raw vectors (IndexIVFFlat)
-    "ivfpq_ivfflat_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.POINTER(c_handle)]),
-    "ivfpq_ivfflat_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfflat_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
-    "ivfpq_ivfflat_set_trained": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_ivfflat_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_i64p]),
-    "ivfpq_ivfflat_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p]),
-    "ivfpq_ivfflat_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfflat_set_nprobe": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_ivfflat_get_nprobe": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfflat_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_ivfflat_search_preassigned": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_i64p,
-                                                        c_f32p, c_f32p, c_i64p]),
-    "ivfpq_ivfflat_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_ivfflat_search_preassigned_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p,
-                                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_ivfflat_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_ivfflat_is_trained": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfflat_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 3),
-    "ivfpq_ivfflat_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_ivfflat_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
-    "ivfpq_ivfflat_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_f32p, c_i64p]),
+    **_family("ivfpq_ivfflat_", **_ivf(c_f32p), create=_create(4), get_dims=_dims(3), train=TRAIN,
+              set_trained=F32_ARRAY),
     # flat scalar quantizer (IndexScalarQuantizer)
-    "ivfpq_sq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(c_handle)]),
-    "ivfpq_sq_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_sq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
-    "ivfpq_sq_set_trained": (ctypes.c_int, [c_handle, c_f32p, ctypes.c_int64]),
-    "ivfpq_sq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
-    "ivfpq_sq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_sq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
-    "ivfpq_sq_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_sq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_sq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_sq_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_sq_is_trained": (ctypes.c_int, [c_handle]),
-    "ivfpq_sq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 4),
-    "ivfpq_sq_get_trained": (ctypes.c_int, [c_handle, c_f32p, c_i64p]),
-    "ivfpq_sq_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
-    "ivfpq_sq_encode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_u8p]),
-    "ivfpq_sq_decode": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, c_f32p]),
+    **_family(
+        "ivfpq_sq_", create=_create(4), get_dims=_dims(4), is_trained=HANDLE, train=F32_ROWS,
+        set_trained=_rc(c_handle, c_f32p, _i64), get_trained=GET_TRAINED, add=F32_ROWS, add_device=ADD_DEVICE,
+        add_codes=U8_ROWS, get_codes=GET_CODES, encode=_rc(c_handle, _i64, c_f32p, c_u8p),
+        decode=_rc(c_handle, _i64, c_u8p, c_f32p), get_plan=_rc(_i64, _i64, _int, _intp, _intp, c_i64p)),
     # IVF over scalar-quantizer codes (IndexIVFScalarQuantizer)
-    "ivfpq_ivfsq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.POINTER(c_handle)]),
-    "ivfpq_ivfsq_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfsq_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_uint64]),
-    "ivfpq_ivfsq_set_trained": (ctypes.c_int, [c_handle, c_f32p, c_f32p, ctypes.c_int64]),
-    "ivfpq_ivfsq_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, c_i64p]),
-    "ivfpq_ivfsq_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_void_p]),
-    "ivfpq_ivfsq_add_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, c_i64p, c_u8p, c_i64p]),
-    "ivfpq_ivfsq_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfsq_set_nprobe": (ctypes.c_int, [c_handle, ctypes.c_int]),
-    "ivfpq_ivfsq_get_nprobe": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfsq_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_ivfsq_search_preassigned": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_i64p,
-                                                      c_f32p, c_f32p, c_i64p]),
-    "ivfpq_ivfsq_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_ivfsq_search_preassigned_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p,
-                                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_ivfsq_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_ivfsq_is_trained": (ctypes.c_int, [c_handle]),
-    "ivfpq_ivfsq_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 6),
-    "ivfpq_ivfsq_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_ivfsq_get_trained": (ctypes.c_int, [c_handle, c_f32p, c_i64p]),
-    "ivfpq_ivfsq_get_list_sizes": (ctypes.c_int, [c_handle, c_i64p]),
-    "ivfpq_ivfsq_get_list": (ctypes.c_int, [c_handle, ctypes.c_int, c_u8p, c_i64p]),
+    **_family("ivfpq_ivfsq_", **_ivf(c_u8p), create=_create(6), get_dims=_dims(6), train=TRAIN,
+              set_trained=_rc(c_handle, c_f32p, c_f32p, _i64), get_trained=GET_TRAINED, add_codes=ADD_LISTED),
     # flat binary codes (IndexBinaryFlat)
-    "ivfpq_bin_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_handle)]),
-    "ivfpq_bin_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_bin_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_bin_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p]),
-    "ivfpq_bin_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_bin_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_u8p, ctypes.c_int, c_i32p, c_i64p]),
-    "ivfpq_bin_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_bin_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_bin_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 2),
-    "ivfpq_bin_get_codes": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_u8p]),
-    "ivfpq_bin_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                                          ctypes.POINTER(ctypes.c_int), c_i64p, c_i64p]),
+    **_family(
+        "ivfpq_bin_", create=_create(2), get_dims=_dims(2), add=U8_ROWS, add_device=ADD_DEVICE, get_codes=GET_CODES,
+        search=_rc(c_handle, _i64, c_u8p, _int, c_i32p, c_i64p),
+        get_plan=_rc(_int, _i64, _i64, _int, _intp, _intp, _intp, c_i64p, c_i64p)),
     # flat fp32 rows (IndexFlat / IndexFlatL2 / IndexFlatIP)
-    "ivfpq_flat_index_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_handle)]),
-    "ivfpq_flat_index_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_flat_index_reset": (ctypes.c_int, [c_handle]),
-    "ivfpq_flat_index_add": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p]),
-    "ivfpq_flat_index_add_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_flat_index_search": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, c_f32p, c_i64p]),
-    "ivfpq_flat_index_search_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ivfpq_flat_index_ntotal": (ctypes.c_int64, [c_handle]),
-    "ivfpq_flat_index_get_dims": (ctypes.c_int, [c_handle] + [ctypes.POINTER(ctypes.c_int)] * 2),
-    "ivfpq_flat_index_get_rows": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_int64, c_f32p]),
-    "ivfpq_flat_index_get_stats": (ctypes.c_int, [c_handle, c_i64p, c_i64p, c_i64p]),
-    "ivfpq_flat_index_set_range_rows": (ctypes.c_int, [c_handle, ctypes.c_int64]),
-    "ivfpq_flat_index_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                                 ctypes.POINTER(ctypes.c_int), c_i64p, ctypes.POINTER(ctypes.c_int),
-                                                 ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                                                 ctypes.POINTER(ctypes.c_int), c_i64p]),
+    **_family(
+        "ivfpq_flat_index_", create=_create(3), get_dims=_dims(2), add=F32_ROWS, add_device=ADD_DEVICE,
+        get_rows=_rc(c_handle, _i64, _i64, c_f32p), get_stats=_rc(c_handle, c_i64p, c_i64p, c_i64p),
+        set_range_rows=SET_I64,
+        get_plan=_rc(_i64, _i64, _int, _i64, _intp, c_i64p, _intp, _intp, _intp, _intp, c_i64p)),
     # stand-alone k-means (Kmeans / Clustering)
-    "ivfpq_clus_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.POINTER(c_handle)]),
-    "ivfpq_clus_free": (ctypes.c_int, [c_handle]),
-    "ivfpq_clus_train": (ctypes.c_int, [c_handle, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_uint64, c_f32p]),
-    "ivfpq_clus_train_device": (ctypes.c_int, [c_handle, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
-    "ivfpq_clus_get_centroids": (ctypes.c_int, [c_handle, c_f32p]),
-    "ivfpq_clus_get_stats": (ctypes.c_int, [c_handle, ctypes.POINTER(ctypes.c_int),
-                                            ctypes.POINTER(ctypes.c_double), c_i64p]),
-    "ivfpq_clus_set_pass_rows": (ctypes.c_int, [c_handle, ctypes.c_int64]),
-    "ivfpq_clus_rand_perm_prefix": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, c_i64p]),
+    "ivfpq_clus_create": _create(5),
+    "ivfpq_clus_free": HANDLE,
+    "ivfpq_clus_train": _rc(c_handle, _i64, c_f32p, _int, _int, _u64, c_f32p),
+    "ivfpq_clus_train_device": _rc(c_handle, _i64, _vp, _int, _int, _u64, c_f32p, _vp),
+    "ivfpq_clus_get_centroids": F32_ARRAY,
+    "ivfpq_clus_get_stats": _rc(c_handle, _intp, _f64p, c_i64p),
+    "ivfpq_clus_set_pass_rows": SET_I64,
+    "ivfpq_clus_rand_perm_prefix": _rc(_i64, _i64, _u64, c_i64p),
     # how the host cuts a batch into chunks (host arithmetic; faiss_amd.index.*_split)
-    "ivfpq_ivf_get_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
-                                          ctypes.POINTER(ctypes.c_int)]),
-    "ivfpq_ivf_get_query_chunk": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 7 + [c_i64p]),
-    "ivfpq_ivf_get_pass_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64p]),
-    "ivfpq_sq_get_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                         ctypes.POINTER(ctypes.c_int), c_i64p]),
-    "ivfpq_get_query_chunk": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 6 + [c_i64p]),
-    "ivfpq_host_get_pass_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_i64p]),
-    "ivfpq_flat_search_get_query_chunk": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_i64p]),
-    "ivfpq_kmeans_get_assign_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_i64p]),
+    "ivfpq_ivf_get_plan": _rc(_int, _i64, _intp, _intp),
+    "ivfpq_ivf_get_query_chunk": _rc(_i64, *[_int] * 7, c_i64p),
+    "ivfpq_ivf_get_pass_rows": _rc(_i64, _int, _int, _int, c_i64p),
+    "ivfpq_get_query_chunk": _rc(_i64, *[_int] * 6, c_i64p),
+    "ivfpq_host_get_pass_rows": QUERY_CHUNK,
+    "ivfpq_flat_search_get_query_chunk": QUERY_CHUNK,
+    "ivfpq_kmeans_get_assign_rows": _rc(_i64, _int, c_i64p),
 }
 
 
@@ -308,6 +209,19 @@ def load():
             fn.argtypes = args
         _lib = lib
         return _lib
+
+
+class Family:
+    """The functions of one C-ABI family: ``Family("ivfpq_pq_").search`` is ``ivfpq_pq_search``.  Each is
+    looked up in the loaded library at its first use and kept, so a later call costs one attribute read
+    (``load()`` takes a lock)."""
+
+    def __init__(self, prefix):
+        self.prefix = prefix
+
+    def __getattr__(self, name):  # reached only for a name that is not kept yet
+        fn = self.__dict__[name] = getattr(load(), self.prefix + name)
+        return fn
 
 
 def check(rc: int):

@@ -39,21 +39,10 @@ import re
 import numpy as np
 
 from . import _lib, faiss_io
+from ._handle import MAX_K, _default_device, _f32, _HandleIndex, _ids_ptr, _ListsView, _ptr  # noqa: F401
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-MAX_K = 1024
-
-
-def _f32(x, d=None, name="x"):
-    a = np.ascontiguousarray(x, dtype=np.float32)
-    if a.ndim != 2 or (d is not None and a.shape[1] != d):
-        raise RuntimeError(f"{name} must be a float32 matrix with {d} columns, got shape {a.shape}")
-    return a
-
-
-def _ptr(a, t):
-    return a.ctypes.data_as(t)
 
 
 def swig_ptr(a):
@@ -80,18 +69,7 @@ def get_num_gpus():
     return int(_lib.load().ivfpq_device_count())
 
 
-def _default_device():
-    try:
-        import torch
-
-        if torch.cuda.is_available():
-            return torch.cuda.current_device()
-    except Exception:
-        pass
-    return 0
-
-
-class IndexFlat:
+class IndexFlat(_HandleIndex):
     """Exact search over the raw vectors (faiss.IndexFlat(d, metric)): L2 returns the k
     smallest distances ascending, inner product the k largest descending, ties by label (the
     row position), missing results (FLT_MAX | -FLT_MAX, -1).
@@ -108,28 +86,21 @@ class IndexFlat:
     matrix-core scan over the image (csrc/flat_scan.hip); its results are those of the
     stateless ``ivfpq_flat_search`` bit for bit."""
 
+    _c = _lib.Family("ivfpq_flat_index_")
+    _faiss_name = "IndexFlat"
     is_trained = True
 
     def __init__(self, d, metric=METRIC_L2, device=None):
-        d = int(d)  # (d >= 1 is checked where the device image is created: an IVF index validates its own d)
+        # (d >= 1 is checked where the device image is created: an IVF index validates its own d)
         if metric not in (METRIC_L2, METRIC_INNER_PRODUCT):
             raise RuntimeError(f"IndexFlat: unknown metric {metric}")
-        self.d = d
-        self.metric_type = metric
-        self.device = _default_device() if device is None else int(device)
-        self.verbose = False
+        _HandleIndex.__init__(self, d, metric, device)
         self._h = None
-        self._buf = np.empty((0, max(d, 0)), np.float32)  # host rows [0, _nhost); _buf.shape[0] is the capacity
+        self._buf = np.empty((0, max(self.d, 0)), np.float32)  # host rows [0, _nhost); _buf.shape[0] is the capacity
         self._nhost = 0   # rows the host buffer holds (a prefix of the index)
         self._ndev = 0    # rows the device image holds (a prefix of the index)
         self._ntotal = 0
         self._range_rows = 0
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_flat_index_free(h)
-            self._h = None
 
     @property
     def ntotal(self):
@@ -156,25 +127,22 @@ class IndexFlat:
             return
         self._host_reserve(n)
         out = self._buf[self._nhost:self._ntotal]
-        _lib.check(_lib.load().ivfpq_flat_index_get_rows(self._h, self._nhost, n, _ptr(out, _lib.c_f32p)))
+        _lib.check(self._c.get_rows(self._h, self._nhost, n, _ptr(out)))
         self._nhost = self._ntotal
 
-    def _sync_device(self):
+    def _handle(self):
         """Create the device image at its first use and upload the rows it lacks."""
-        L = _lib.load()
         if self._h is None:
-            h = _lib.c_handle()
-            _lib.check(L.ivfpq_flat_index_create(self.device, self.d, self.metric_type, ctypes.byref(h)))
-            self._h = h
+            self._create(self.device, self.d, self.metric_type)
             self._ndev = 0
             if self._range_rows:
-                _lib.check(L.ivfpq_flat_index_set_range_rows(h, self._range_rows))
+                _lib.check(self._c.set_range_rows(self._h, self._range_rows))
         n = self._ntotal - self._ndev
         if n > 0:
             rows = self._buf[self._ndev:self._ntotal]
-            _lib.check(L.ivfpq_flat_index_add(self._h, n, _ptr(rows, _lib.c_f32p)))
+            _lib.check(self._c.add(self._h, n, _ptr(rows)))
             self._ndev = self._ntotal
-        return L
+        return self._h
 
     @property
     def xb(self):
@@ -189,25 +157,19 @@ class IndexFlat:
         self._nhost += x.shape[0]
         self._ntotal = self._nhost
 
-    def add_with_ids(self, x, ids):
-        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
-
     def add_device(self, x, stream=None):
         """add with the vectors already in HBM (torch float32 CUDA tensor [n, d]): appended
         straight to the device image; returns once the rows are in place."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        L = self._sync_device()
-        _lib.check(L.ivfpq_flat_index_add_device(self._h, n, x.data_ptr(),
-                                                 ctypes.c_void_p(self._stream(x, stream))))
-        self._ntotal += n
+        _HandleIndex.add_device(self, x, stream)
+        self._ntotal += x.shape[0]
         self._ndev = self._ntotal
+
+    def _faiss_bytes(self):
+        return faiss_io.serialize_flat(self.d, self.metric_type, self.xb.reshape(-1, self.d))
 
     def reset(self):
         if self._h is not None:
-            _lib.check(_lib.load().ivfpq_flat_index_reset(self._h))
+            _lib.check(self._c.reset(self._h))
         self._buf = np.empty((0, self.d), np.float32)
         self._nhost = self._ndev = self._ntotal = 0
 
@@ -234,7 +196,7 @@ class IndexFlat:
             raise RuntimeError("negative range size")
         self._range_rows = rows
         if self._h is not None:
-            _lib.check(_lib.load().ivfpq_flat_index_set_range_rows(self._h, rows))
+            _lib.check(self._c.set_range_rows(self._h, rows))
 
     def uploaded_rows(self):
         """Rows copied from the host into the device image since it was created (the image is
@@ -242,35 +204,8 @@ class IndexFlat:
         if self._h is None:
             return 0
         out = ctypes.c_int64(0)
-        _lib.check(_lib.load().ivfpq_flat_index_get_stats(self._h, ctypes.byref(out), None, None))
+        _lib.check(self._c.get_stats(self._h, ctypes.byref(out), None, None))
         return out.value
-
-    # ------------------------------------------------------------ search path
-    def search(self, x, k):
-        x = _f32(x, self.d)
-        n = x.shape[0]
-        if not 1 <= int(k) <= MAX_K:
-            raise RuntimeError(f"k must be in [1, {MAX_K}]")
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        L = self._sync_device()
-        _lib.check(L.ivfpq_flat_index_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                             _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
-        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
-        import torch
-
-        self._check_k(k)
-        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
-        D, I = self._dev_outputs(x, k, D, I)
-        L = self._sync_device()
-        _lib.check(L.ivfpq_flat_index_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                                    I.data_ptr(),
-                                                    ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
 
 
 def flat_search_plan(nq, nb, k, range_rows=0):
@@ -381,38 +316,8 @@ class _ProductQuantizer:
         return self._o.codebook()[m, j].copy()
 
 
-class _InvertedLists:
-    """index.invlists view (faiss ArrayInvertedLists read API)."""
-
-    def __init__(self, owner):
-        self._o = owner
-
-    @property
-    def nlist(self):
-        return self._o.nlist
-
-    @property
-    def code_size(self):
-        return self._o.M
-
-    def list_sizes(self):
-        out = np.empty(self._o.nlist, np.int64)
-        _lib.check(_lib.load().ivfpq_get_list_sizes(self._o._h, _ptr(out, _lib.c_i64p)))
-        return out
-
-    def list_size(self, l):
-        return int(self.list_sizes()[l])
-
-    def _get(self, l):
-        n = self.list_size(l)
-        codes = np.empty((n, self._o.M), np.uint8)
-        ids = np.empty(n, np.int64)
-        _lib.check(_lib.load().ivfpq_get_list(self._o._h, int(l), _ptr(codes, _lib.c_u8p),
-                                              _ptr(ids, _lib.c_i64p)))
-        return codes, ids
-
-    def get_codes(self, l):
-        return self._get(l)[0].reshape(-1)
+class _InvertedLists(_ListsView):
+    """index.invlists of an IndexIVFPQ: the codes of a list are its rows' PQ codes, M bytes each."""
 
     def export(self):
         """All lists at once: (list_no int64 [ntotal], codes uint8 [ntotal][M], ids
@@ -423,21 +328,9 @@ class _InvertedLists:
         codes = np.empty((tot, self._o.M), np.uint8)
         ids = np.empty(tot, np.int64)
         off = np.concatenate([[0], np.cumsum(sizes)])
-        L = _lib.load()
         for l in np.nonzero(sizes)[0]:
-            _lib.check(L.ivfpq_get_list(self._o._h, int(l), _ptr(codes[off[l]:], _lib.c_u8p),
-                                        _ptr(ids[off[l]:], _lib.c_i64p)))
+            _lib.check(self._o._c.get_list(self._o._h, int(l), _ptr(codes[off[l]:]), _ptr(ids[off[l]:])))
         return np.repeat(np.arange(self._o.nlist, dtype=np.int64), sizes), codes, ids
-
-    def get_ids(self, l):
-        return self._get(l)[1]
-
-    def imbalance_factor(self):
-        """faiss InvertedLists::imbalance_factor: nlist * sum(n_l^2) / ntotal^2."""
-        s = self.list_sizes().astype(np.float64)
-        tot = s.sum()
-        return float(len(s) * (s * s).sum() / (tot * tot)) if tot else 0.0
-
 
 
 def overlap_built():
@@ -445,153 +338,78 @@ def overlap_built():
     for callers of the r04 interface, where it was a build option)."""
     return bool(_lib.load().ivfpq_overlap_built())
 
-class IndexIVFPQ:
-    """faiss.IndexIVFPQ (by_residual; METRIC_L2 with precomputed tables, or
-    METRIC_INNER_PRODUCT) on one MI355X."""
 
-    by_residual = True
-    use_precomputed_table = 1
-    polysemous_ht = 0
+def _pq_codebook(index):
+    """codebook() of the two product-quantizer indexes: float32 [M][2^nbits][d/M], fetched once and kept
+    until the next train / set_trained clears ``_codebook_cache``."""
+    if index._codebook_cache is None:
+        cb = np.empty((index.M, 1 << index.nbits, index.d // index.M), np.float32)
+        _lib.check(index._c.get_codebook(index._h, _ptr(cb)))
+        index._codebook_cache = cb
+    return index._codebook_cache
 
-    def __init__(self, quantizer, d, nlist, M, nbits=8, metric=METRIC_L2, device=None, _handle=None):
-        self.d = int(d)
+
+class _IVFIndex(_HandleIndex):
+    """What the three indexes over inverted lists share: the coarse quantizer, ``nprobe``, adds with
+    labels and the searches of preassigned lists.  ``Dq`` is passed on where it is given; each class
+    says whether its scan reads it."""
+
+    def __init__(self, quantizer, d, nlist, metric, device):
+        _HandleIndex.__init__(self, d, metric, device)
         self.nlist = int(nlist)
-        self.M = int(M)
-        self.nbits = int(nbits)
-        self.metric_type = metric
-        self.device = _default_device() if device is None else int(device)
         if quantizer is None:
             quantizer = (IndexFlatIP if metric == METRIC_INNER_PRODUCT else IndexFlatL2)(d, self.device)
         self.quantizer = quantizer
         self.parallel_mode = 0  # accepted for faiss_retriever.py:71; queries are always independent
-        self.verbose = False
         self.niter_coarse = 25
-        self.niter_pq = 25
         self.seed = 1234
-        L = _lib.load()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            h = _lib.c_handle()
-            _lib.check(L.ivfpq_create(self.d, self.nlist, self.M, self.nbits, metric, self.device, ctypes.byref(h)))
-            self._h = h
-        self.pq = _ProductQuantizer(self)
-        self.invlists = _InvertedLists(self)
-        self._codebook_cache = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_free(h)
-            self._h = None
-
-    # ------------------------------------------------------------ properties
-    @property
-    def ntotal(self):
-        return int(_lib.load().ivfpq_ntotal(self._h))
-
-    @property
-    def is_trained(self):
-        return bool(_lib.load().ivfpq_is_trained(self._h))
 
     @property
     def nprobe(self):
-        return int(_lib.load().ivfpq_get_nprobe(self._h))
+        return int(self._c.get_nprobe(self._h))
 
     @nprobe.setter
     def nprobe(self, p):
-        _lib.check(_lib.load().ivfpq_set_nprobe(self._h, int(p)))
-
-    @property
-    def code_size(self):
-        return self.M
-
-    def codebook(self):
-        if self._codebook_cache is None:
-            cb = np.empty((self.M, 1 << self.nbits, self.d // self.M), np.float32)
-            _lib.check(_lib.load().ivfpq_get_codebook(self._h, _ptr(cb, _lib.c_f32p)))
-            self._codebook_cache = cb
-        return self._codebook_cache
+        _lib.check(self._c.set_nprobe(self._h, int(p)))
 
     def centroids(self):
         c = np.empty((self.nlist, self.d), np.float32)
-        _lib.check(_lib.load().ivfpq_get_centroids(self._h, _ptr(c, _lib.c_f32p)))
+        _lib.check(self._c.get_centroids(self._h, _ptr(c)))
         return c
-
-    @property
-    def precomputed_table(self):
-        t = np.empty((self.nlist, self.M, 1 << self.nbits), np.float32)
-        _lib.check(_lib.load().ivfpq_get_precomputed_table(self._h, _ptr(t, _lib.c_f32p)))
-        return t.reshape(-1)
 
     def _sync_quantizer(self):
         if isinstance(self.quantizer, IndexFlatL2):  # IndexFlatIP too
             self.quantizer.reset()
             self.quantizer.add(self.centroids())
 
-    # ----------------------------------------------------------- build path
-    def train(self, x):
-        x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_coarse,
-                                           self.niter_pq, self.seed))
-        self._codebook_cache = None
-        self._sync_quantizer()
-
-    def set_trained(self, centroids, codebook):
-        """Install trained quantizers (coarse centroids [nlist][d], PQ codebook [M][256][d/M])."""
-        c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
-        cb = np.ascontiguousarray(codebook, np.float32).reshape(-1)
-        if cb.size != self.M * (1 << self.nbits) * (self.d // self.M):
-            raise RuntimeError("codebook has the wrong size")
-        _lib.check(_lib.load().ivfpq_set_trained(self._h, _ptr(c, _lib.c_f32p), _ptr(cb, _lib.c_f32p)))
-        self._codebook_cache = None
-        self._sync_quantizer()
-
     def add(self, x):
-        x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), None))
+        self.add_with_ids(x, None)
 
     def add_with_ids(self, x, ids):
         x = _f32(x, self.d)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        if ids.shape[0] != x.shape[0]:
-            raise RuntimeError("ids and x have different lengths")
-        _lib.check(_lib.load().ivfpq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(ids, _lib.c_i64p)))
+        _lib.check(self._c.add(self._h, x.shape[0], _ptr(x), _ids_ptr(ids, x.shape[0], "x")))
 
-    def add_preencoded(self, list_no, codes, ids=None):
+    def _add_listed(self, fn, list_no, codes, ids):
+        """Append codes uint8 [n][code_size] to the lists ``list_no`` [n] with labels ``ids`` (None: sequential)."""
         list_no = np.ascontiguousarray(list_no, np.int64).reshape(-1)
-        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.M)
+        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.code_size)
         n = list_no.shape[0]
         if codes.shape[0] != n:
             raise RuntimeError("codes and list_no have different lengths")
-        idp = None
+        _lib.check(fn(self._h, n, _ptr(list_no), _ptr(codes), _ids_ptr(ids, n, "list_no")))
+
+    def add_device(self, x, ids=None, stream=None):
+        """add / add_with_ids with the vectors already in HBM (torch float32 CUDA
+        tensor [n, d]; ids: int64 CUDA tensor [n] or None for sequential ids).
+        Assignment, encoding and the list-image merge run on the GPU; returns
+        once the new image is in place."""
+        import torch
+
+        n = self._dev_rows(x)
         if ids is not None:
-            ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-            idp = _ptr(ids, _lib.c_i64p)
-        _lib.check(_lib.load().ivfpq_add_preencoded(self._h, n, _ptr(list_no, _lib.c_i64p),
-                                                    _ptr(codes, _lib.c_u8p), idp))
-
-    def reset(self):
-        _lib.check(_lib.load().ivfpq_reset(self._h))
-
-    def set_list_range(self, lo, hi):
-        """Keep and scan only inverted lists [lo, hi) (list-range sharding)."""
-        _lib.check(_lib.load().ivfpq_set_list_range(self._h, int(lo), int(hi)))
-
-    # ------------------------------------------------------------ search path
-    def _check_k(self, k):
-        if not 1 <= int(k) <= MAX_K:
-            raise RuntimeError(f"k must be in [1, {MAX_K}], got {k}")
-
-    def search(self, x, k):
-        x = _f32(x, self.d)
-        self._check_k(k)
-        n = x.shape[0]
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                            _ptr(I, _lib.c_i64p)))
-        return D, I
+            self._check_dev(ids, "ids", torch.int64, (n,))
+        _lib.check(self._c.add_device(self._h, n, x.data_ptr(), ids.data_ptr() if ids is not None else None,
+                                      ctypes.c_void_p(self._stream(x, stream))))
 
     def search_preassigned(self, *args):
         """Either ``search_preassigned(x, k, Iq, Dq=None) -> (D, I)`` or the
@@ -616,17 +434,100 @@ class IndexIVFPQ:
         Iq = np.ascontiguousarray(Iq, np.int64).reshape(n, -1)
         if Iq.shape[1] != self.nprobe:
             raise RuntimeError(f"Iq must have nprobe={self.nprobe} columns, got {Iq.shape[1]}")
-        Dqp = None
         if Dq is not None:
-            Dq = np.ascontiguousarray(Dq, np.float32).reshape(Iq.shape)
-            Dqp = _ptr(Dq, _lib.c_f32p)
+            Dq = _ptr(np.ascontiguousarray(Dq, np.float32).reshape(Iq.shape))
         D = np.empty((n, k), np.float32)
         I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_search_preassigned(self._h, n, _ptr(x, _lib.c_f32p), int(k),
-                                                        _ptr(Iq, _lib.c_i64p), Dqp, _ptr(D, _lib.c_f32p),
-                                                        _ptr(I, _lib.c_i64p)))
+        _lib.check(self._c.search_preassigned(self._h, n, _ptr(x), int(k), _ptr(Iq), Dq, _ptr(D), _ptr(I)))
         return D, I
 
+    def search_preassigned_device(self, x, k, Iq, Dq=None, D=None, I=None, stream=None):
+        """search_preassigned with HBM-resident inputs."""
+        return self._preassigned_device(self._c.search_preassigned_device, x, k, Iq, Dq, D, I, stream)
+
+    def _preassigned_device(self, fn, x, k, Iq, Dq, D, I, stream, *token):
+        import torch
+
+        self._check_k(k)
+        n = self._dev_rows(x)
+        self._check_dev(Iq, "Iq", torch.int64, (n, self.nprobe))
+        if Dq is not None:
+            self._check_dev(Dq, "Dq", torch.float32, (n, self.nprobe))
+        D, I = self._dev_outputs(x, k, D, I)
+        _lib.check(fn(self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
+                      D.data_ptr(), I.data_ptr(), *token, ctypes.c_void_p(self._stream(x, stream))))
+        return D, I
+
+
+class IndexIVFPQ(_IVFIndex):
+    """faiss.IndexIVFPQ (by_residual; METRIC_L2 with precomputed tables, or
+    METRIC_INNER_PRODUCT) on one MI355X.  Device searches of one index may be issued on
+    different streams without synchronizing: the library orders each search after those still
+    in flight on other streams, or, with ``inflight`` on, lets them overlap."""
+
+    _c = _lib.Family("ivfpq_")
+    _faiss_name = "IndexIVFPQ"
+    by_residual = True
+    use_precomputed_table = 1
+    polysemous_ht = 0
+
+    def __init__(self, quantizer, d, nlist, M, nbits=8, metric=METRIC_L2, device=None, _handle=None):
+        _IVFIndex.__init__(self, quantizer, d, nlist, metric, device)
+        self.M = int(M)
+        self.nbits = int(nbits)
+        self.niter_pq = 25
+        if _handle is not None:
+            self._h = _handle
+        else:
+            self._create(self.d, self.nlist, self.M, self.nbits, metric, self.device)
+        self.pq = _ProductQuantizer(self)
+        self.invlists = _InvertedLists(self)
+        self._codebook_cache = None
+
+    @property
+    def code_size(self):
+        return self.M
+
+    def codebook(self):
+        return _pq_codebook(self)
+
+    @property
+    def precomputed_table(self):
+        t = np.empty((self.nlist, self.M, 1 << self.nbits), np.float32)
+        _lib.check(self._c.get_precomputed_table(self._h, _ptr(t)))
+        return t.reshape(-1)
+
+    # ----------------------------------------------------------- build path
+    def train(self, x):
+        x = _f32(x, self.d)
+        _lib.check(self._c.train(self._h, x.shape[0], _ptr(x), self.niter_coarse, self.niter_pq, self.seed))
+        self._codebook_cache = None
+        self._sync_quantizer()
+
+    def set_trained(self, centroids, codebook):
+        """Install trained quantizers (coarse centroids [nlist][d], PQ codebook [M][256][d/M])."""
+        c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
+        cb = np.ascontiguousarray(codebook, np.float32).reshape(-1)
+        if cb.size != self.M * (1 << self.nbits) * (self.d // self.M):
+            raise RuntimeError("codebook has the wrong size")
+        _lib.check(self._c.set_trained(self._h, _ptr(c), _ptr(cb)))
+        self._codebook_cache = None
+        self._sync_quantizer()
+
+    def add_preencoded(self, list_no, codes, ids=None):
+        self._add_listed(self._c.add_preencoded, list_no, codes, ids)
+
+    def set_list_range(self, lo, hi):
+        """Keep and scan only inverted lists [lo, hi) (list-range sharding)."""
+        _lib.check(self._c.set_list_range(self._h, int(lo), int(hi)))
+
+    def _faiss_bytes(self):
+        inv = self.invlists
+        lists = [(inv.get_ids(l), inv.get_codes(l).reshape(-1, self.code_size)) for l in range(self.nlist)]
+        return faiss_io.serialize_ivfpq(self.d, self.nlist, self.nprobe, self.M, self.nbits, self.metric_type,
+                                        self.centroids(), self.codebook(), lists)
+
+    # ------------------------------------------------------------ search path
     def serve_request(self, msg, batch_size, dim, with_lists=False, nprobe=None, out=None):
         """One FaissServer request (RALM wire format, ``faiss_amd.wire``) in, the
         encoded answer out: decode + search (or search_preassigned) + encode in
@@ -650,9 +551,8 @@ class IndexIVFPQ:
         if not with_lists and nprobe is not None:
             self.nprobe = np_
         try:
-            _lib.check(_lib.load().ivfpq_serve_request(self._h, _ptr(buf, _lib.c_u8p), buf.size,
-                                                       int(bool(with_lists)), int(batch_size), int(dim), np_,
-                                                       _ptr(ans, _lib.c_u8p), ans.size, ctypes.byref(ln)))
+            _lib.check(self._c.serve_request(self._h, _ptr(buf), buf.size, int(bool(with_lists)), int(batch_size),
+                                             int(dim), np_, _ptr(ans), ans.size, ctypes.byref(ln)))
         finally:
             if self.nprobe != saved:
                 self.nprobe = saved
@@ -663,51 +563,16 @@ class IndexIVFPQ:
 
     def set_timing(self, on=True, lists_only=False):
         """Record HIP events around every stage (or, lists_only, around the list-scan kernel alone)."""
-        _lib.check(_lib.load().ivfpq_set_timing(self._h, (2 if lists_only else 1) if on else 0))
+        _lib.check(self._c.set_timing(self._h, (2 if lists_only else 1) if on else 0))
 
     def get_timing(self):
         """{stage: (total_ms, launches)} since the last call (waits for the events)."""
         ms = (ctypes.c_double * len(self.STAGES))()
         cnt = (ctypes.c_int64 * len(self.STAGES))()
-        _lib.check(_lib.load().ivfpq_get_timing(self._h, ms, cnt))
+        _lib.check(self._c.get_timing(self._h, ms, cnt))
         return {s: (ms[i], cnt[i]) for i, s in enumerate(self.STAGES)}
 
     # ------------------------------------------------- device (torch) entry points
-    def _check_dev(self, t, name, dtype, shape):
-        """The C-ABI takes raw device pointers: anything but a contiguous tensor of
-        the exact dtype and shape on this index's device would be read or written
-        out of bounds, so it is rejected here (as the host path rejects bad arrays)."""
-        import torch
-
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-        if t.device.index != self.device:
-            raise RuntimeError(f"{name} is on cuda:{t.device.index}, the index on cuda:{self.device}")
-        if t.dtype != dtype:
-            raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
-        if tuple(t.shape) != tuple(shape):
-            raise RuntimeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{name} must be contiguous")
-        return t
-
-    def _dev_outputs(self, x, k, D, I):
-        import torch
-
-        n = x.shape[0]
-        if D is None:
-            D = torch.empty((n, k), dtype=torch.float32, device=x.device)
-        if I is None:
-            I = torch.empty((n, k), dtype=torch.int64, device=x.device)
-        self._check_dev(D, "D", torch.float32, (n, k))
-        self._check_dev(I, "I", torch.int64, (n, k))
-        return D, I
-
-    def _stream(self, x, stream):
-        import torch
-
-        return stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-
     @property
     def inflight(self):
         """Batches in flight: True lets device searches issued on different
@@ -716,17 +581,17 @@ class IndexIVFPQ:
         after those still in flight on other streams.  Results are the same in
         both modes (tests/test_gpu_parity.py
         test_batches_in_flight_stress)."""
-        return bool(_lib.load().ivfpq_get_inflight(self._h))
+        return bool(self._c.get_inflight(self._h))
 
     @inflight.setter
     def inflight(self, on):
-        _lib.check(_lib.load().ivfpq_set_inflight(self._h, int(bool(on))))
+        _lib.check(self._c.set_inflight(self._h, int(bool(on))))
 
     def error_count(self):
         """Index-check violations counted by the merge kernels since creation
         (ivfpq_get_error_count; 0 on a correct run).  Waits for in-flight searches."""
         out = ctypes.c_int64(0)
-        _lib.check(_lib.load().ivfpq_get_error_count(self._h, ctypes.byref(out)))
+        _lib.check(self._c.get_error_count(self._h, ctypes.byref(out)))
         return out.value
 
     def repair_stats(self):
@@ -734,14 +599,14 @@ class IndexIVFPQ:
         partial-list entry this batch's scan did not leave there, and the probes the merge
         rescanned because of one (ivfpq_get_repair_stats).  Waits for in-flight searches."""
         st, rp = ctypes.c_int64(0), ctypes.c_int64(0)
-        _lib.check(_lib.load().ivfpq_get_repair_stats(self._h, ctypes.byref(st), ctypes.byref(rp)))
+        _lib.check(self._c.get_repair_stats(self._h, ctypes.byref(st), ctypes.byref(rp)))
         return st.value, rp.value
 
     def repair_log(self, max_events=192):
         """The first stale-entry events as dicts (ivfpq_get_repair_log)."""
         buf = (ctypes.c_uint32 * (8 * max_events))()
         n = ctypes.c_int(0)
-        _lib.check(_lib.load().ivfpq_get_repair_log(self._h, buf, int(max_events), ctypes.byref(n)))
+        _lib.check(self._c.get_repair_log(self._h, buf, int(max_events), ctypes.byref(n)))
         out = []
         for e in range(n.value):
             w = buf[8 * e:8 * e + 8]
@@ -753,83 +618,31 @@ class IndexIVFPQ:
     def set_fault_injection(self, every):
         """Test hook: later searches skip the partial-list stores of slots with
         slot % every == 1 (0 = off); results must stay exact (repairs)."""
-        _lib.check(_lib.load().ivfpq_set_fault_injection(self._h, int(every)))
-
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with inputs resident in HBM.  ``x`` is a torch float32 CUDA
-        tensor [n, d] on the index's device; returns torch (D, I) there, launched
-        on ``stream`` (default: torch's current stream).  Searches of one index
-        may be issued on different streams without synchronizing: the library
-        orders each search after those still in flight on other streams, or,
-        with ``inflight`` on, lets them overlap."""
-        import torch
-
-        self._check_k(k)
-        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
-        D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(_lib.load().ivfpq_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                                   I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
+        _lib.check(self._c.set_fault_injection(self._h, int(every)))
 
     def search_preassigned_device(self, x, k, Iq, Dq=None, D=None, I=None, stream=None, tables=None):
         """search_preassigned with HBM-resident inputs.  ``tables``: the token of a
         ``precompute_tables_device(x)`` call for exactly these queries, whose T3
         this search consumes instead of building its own."""
-        import torch
-
-        self._check_k(k)
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        self._check_dev(Iq, "Iq", torch.int64, (n, self.nprobe))
-        if Dq is not None:
-            self._check_dev(Dq, "Dq", torch.float32, (n, self.nprobe))
-        D, I = self._dev_outputs(x, k, D, I)
-        if tables is not None:
-            _lib.check(_lib.load().ivfpq_search_preassigned_tables_device(
-                self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
-                D.data_ptr(), I.data_ptr(), ctypes.c_uint64(int(tables)), ctypes.c_void_p(self._stream(x, stream))))
-        else:
-            _lib.check(_lib.load().ivfpq_search_preassigned_device(
-                self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
-                D.data_ptr(), I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
+        if tables is None:
+            return _IVFIndex.search_preassigned_device(self, x, k, Iq, Dq, D, I, stream)
+        return self._preassigned_device(self._c.search_preassigned_tables_device, x, k, Iq, Dq, D, I, stream,
+                                        ctypes.c_uint64(int(tables)))
 
     def precompute_tables_device(self, x, stream=None):
         """T3 of the queries x (torch CUDA [n, d]) on ``stream``; returns the token
         that ``search_preassigned_device(x, ..., tables=token)`` consumes.  The
         shard flow runs it on a side stream while the coarse step and the probe
         all-gather run.  Up to three tokens can be pending."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
+        n = self._dev_rows(x)
         tok = ctypes.c_uint64(0)
-        _lib.check(_lib.load().ivfpq_precompute_tables_device(self._h, n, x.data_ptr(),
-                                                              ctypes.c_void_p(self._stream(x, stream)),
-                                                              ctypes.byref(tok)))
+        _lib.check(self._c.precompute_tables_device(self._h, n, x.data_ptr(), ctypes.c_void_p(self._stream(x, stream)),
+                                                    ctypes.byref(tok)))
         return tok.value
 
-    def add_device(self, x, ids=None, stream=None):
-        """add / add_with_ids with the vectors already in HBM (torch float32 CUDA
-        tensor [n, d]; ids: int64 CUDA tensor [n] or None for sequential ids).
-        Assignment, encoding and the list-image merge run on the GPU; returns
-        once the new image is in place."""
+    def _coarse_outputs(self, x, n, Iq, Dq):
         import torch
 
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        if ids is not None:
-            self._check_dev(ids, "ids", torch.int64, (n,))
-        _lib.check(_lib.load().ivfpq_add_device(self._h, n, x.data_ptr(), ids.data_ptr() if ids is not None else None,
-                                                ctypes.c_void_p(self._stream(x, stream))))
-
-    def coarse_device(self, x, Iq=None, Dq=None, stream=None):
-        """The coarse quantizer alone: (Dq, Iq) [n, min(nprobe, nlist)] -- L2
-        distances ascending or inner products descending."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
         p = min(self.nprobe, self.nlist)
         if Iq is None:
             Iq = torch.empty((n, p), dtype=torch.int64, device=x.device)
@@ -837,8 +650,15 @@ class IndexIVFPQ:
             Dq = torch.empty((n, p), dtype=torch.float32, device=x.device)
         self._check_dev(Iq, "Iq", torch.int64, (n, p))
         self._check_dev(Dq, "Dq", torch.float32, (n, p))
-        _lib.check(_lib.load().ivfpq_coarse_device(self._h, n, x.data_ptr(), Iq.data_ptr(), Dq.data_ptr(),
-                                                   ctypes.c_void_p(self._stream(x, stream))))
+        return Iq, Dq
+
+    def coarse_device(self, x, Iq=None, Dq=None, stream=None):
+        """The coarse quantizer alone: (Dq, Iq) [n, min(nprobe, nlist)] -- L2
+        distances ascending or inner products descending."""
+        n = self._dev_rows(x)
+        Iq, Dq = self._coarse_outputs(x, n, Iq, Dq)
+        _lib.check(self._c.coarse_device(self._h, n, x.data_ptr(), Iq.data_ptr(), Dq.data_ptr(),
+                                         ctypes.c_void_p(self._stream(x, stream))))
         return Dq, Iq
 
     def coarse_tables_device(self, x, x_tables, Iq=None, Dq=None, stream=None):
@@ -846,83 +666,41 @@ class IndexIVFPQ:
         of this rank's queries ``x`` and T3 of the global batch ``x_tables`` (one
         launch at nlist < 8192).  Returns (Dq, Iq, token); the token goes to
         ``search_preassigned_device(x_tables, ..., tables=token)``."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        nt = x_tables.shape[0] if x_tables.dim() == 2 else -1
-        self._check_dev(x_tables, "x_tables", torch.float32, (nt, self.d))
-        p = min(self.nprobe, self.nlist)
-        if Iq is None:
-            Iq = torch.empty((n, p), dtype=torch.int64, device=x.device)
-        if Dq is None:
-            Dq = torch.empty((n, p), dtype=torch.float32, device=x.device)
-        self._check_dev(Iq, "Iq", torch.int64, (n, p))
-        self._check_dev(Dq, "Dq", torch.float32, (n, p))
+        n = self._dev_rows(x)
+        nt = self._dev_rows(x_tables, "x_tables")
+        Iq, Dq = self._coarse_outputs(x, n, Iq, Dq)
         tok = ctypes.c_uint64(0)
-        _lib.check(_lib.load().ivfpq_coarse_tables_device(self._h, n, x.data_ptr(), Iq.data_ptr(), Dq.data_ptr(), nt,
-                                                          x_tables.data_ptr(), ctypes.c_void_p(self._stream(x, stream)),
-                                                          ctypes.byref(tok)))
+        _lib.check(self._c.coarse_tables_device(self._h, n, x.data_ptr(), Iq.data_ptr(), Dq.data_ptr(), nt,
+                                                x_tables.data_ptr(), ctypes.c_void_p(self._stream(x, stream)),
+                                                ctypes.byref(tok)))
         return Dq, Iq, tok.value
 
 
-# the device-argument checks of the flat index (defined above IndexIVFPQ) are IndexIVFPQ's
-for _name in ("_check_k", "_check_dev", "_dev_outputs", "_stream"):
-    setattr(IndexFlat, _name, getattr(IndexIVFPQ, _name))
-del _name
-
-
-class IndexPQ:
+class IndexPQ(_HandleIndex):
     """faiss.IndexPQ: one product quantizer over the raw vectors, every code
     scanned for every query (beir faiss_search.py:168-224, nbits_experiments_fix_m.py:89).
     Labels are positions: there is no id map, as in Faiss."""
 
+    _c = _lib.Family("ivfpq_pq_")
+    _faiss_name = "IndexPQ"
     polysemous_ht = 0
 
     def __init__(self, d, M, nbits=8, metric=METRIC_L2, device=None):
-        self.d = int(d)
+        _HandleIndex.__init__(self, d, metric, device)
         self.M = int(M)
         self.nbits = int(nbits)
-        self.metric_type = metric
-        self.device = _default_device() if device is None else int(device)
-        self.verbose = False
         self.niter_pq = 25
         self.seed = 1234
-        h = _lib.c_handle()
-        _lib.check(_lib.load().ivfpq_pq_create(self.d, self.M, self.nbits, metric, self.device, ctypes.byref(h)))
-        self._h = h
+        self._create(self.d, self.M, self.nbits, metric, self.device)
         self.pq = _ProductQuantizer(self)
         self._codebook_cache = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_pq_free(h)
-            self._h = None
-
-    @property
-    def ntotal(self):
-        return int(_lib.load().ivfpq_pq_ntotal(self._h))
-
-    @property
-    def is_trained(self):
-        return bool(_lib.load().ivfpq_pq_is_trained(self._h))
 
     @property
     def code_size(self):
         return self.M
 
     def codebook(self):
-        if self._codebook_cache is None:
-            cb = np.empty((self.M, 1 << self.nbits, self.d // self.M), np.float32)
-            _lib.check(_lib.load().ivfpq_pq_get_codebook(self._h, _ptr(cb, _lib.c_f32p)))
-            self._codebook_cache = cb
-        return self._codebook_cache
-
-    def _codes(self, i0, n):
-        out = np.empty((n, self.M), np.uint8)
-        _lib.check(_lib.load().ivfpq_pq_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
-        return out
+        return _pq_codebook(self)
 
     @property
     def codes(self):
@@ -932,7 +710,7 @@ class IndexPQ:
     # ----------------------------------------------------------- build path
     def train(self, x):
         x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_pq_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_pq, self.seed))
+        _lib.check(self._c.train(self._h, x.shape[0], _ptr(x), self.niter_pq, self.seed))
         self._codebook_cache = None
 
     def set_trained(self, codebook):
@@ -940,23 +718,13 @@ class IndexPQ:
         cb = np.ascontiguousarray(codebook, np.float32).reshape(-1)
         if cb.size != self.M * (1 << self.nbits) * (self.d // self.M):
             raise RuntimeError("codebook has the wrong size")
-        _lib.check(_lib.load().ivfpq_pq_set_trained(self._h, _ptr(cb, _lib.c_f32p)))
+        _lib.check(self._c.set_trained(self._h, _ptr(cb)))
         self._codebook_cache = None
-
-    def add(self, x):
-        x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_pq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
-
-    def add_with_ids(self, x, ids):
-        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
 
     def add_codes(self, codes):
         """Append precomputed codes uint8 [n][M]."""
         codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.M)
-        _lib.check(_lib.load().ivfpq_pq_add_codes(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p)))
-
-    def reset(self):
-        _lib.check(_lib.load().ivfpq_pq_reset(self._h))
+        _lib.check(self._c.add_codes(self._h, codes.shape[0], _ptr(codes)))
 
     def reconstruct_n(self, i0, n):
         """Decoded on the host from the codebook and the codes."""
@@ -965,254 +733,56 @@ class IndexPQ:
     def reconstruct(self, i):
         return self.reconstruct_n(i, 1)[0]
 
-    # ------------------------------------------------------------ search path
-    _check_k = IndexIVFPQ._check_k
-    _check_dev = IndexIVFPQ._check_dev
-    _dev_outputs = IndexIVFPQ._dev_outputs
-    _stream = IndexIVFPQ._stream
-
-    def search(self, x, k):
-        x = _f32(x, self.d)
-        self._check_k(k)
-        n = x.shape[0]
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_pq_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                               _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
-        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
-        import torch
-
-        self._check_k(k)
-        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
-        D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(_lib.load().ivfpq_pq_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                                      I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
-
-    def add_device(self, x, stream=None):
-        """add with the vectors already in HBM; returns once the codes are in place."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        _lib.check(_lib.load().ivfpq_pq_add_device(self._h, n, x.data_ptr(),
-                                                   ctypes.c_void_p(self._stream(x, stream))))
+    def _faiss_bytes(self):
+        return faiss_io.serialize_pq(self.d, self.M, self.nbits, self.metric_type, self.codebook(),
+                                     self._codes(0, self.ntotal))
 
 
-class _FlatInvertedLists:
-    """index.invlists of an IndexIVFFlat (faiss ArrayInvertedLists read API): the
-    codes of a list are its vectors' bytes, ``code_size = 4 * d``."""
+class _FlatInvertedLists(_ListsView):
+    """index.invlists of an IndexIVFFlat: the codes of a list are its vectors' bytes,
+    ``code_size = 4 * d``."""
 
-    def __init__(self, owner):
-        self._o = owner
-
-    @property
-    def nlist(self):
-        return self._o.nlist
-
-    @property
-    def code_size(self):
-        return 4 * self._o.d
-
-    def list_sizes(self):
-        out = np.empty(self._o.nlist, np.int64)
-        _lib.check(self._o._fn("get_list_sizes")(self._o._h, _ptr(out, _lib.c_i64p)))
-        return out
-
-    def list_size(self, l):
-        return int(self.list_sizes()[l])
-
-    def _get(self, l):
-        n = self.list_size(l)
-        vecs = np.empty((n, self._o.d), np.float32)
-        ids = np.empty(n, np.int64)
-        _lib.check(self._o._fn("get_list")(self._o._h, int(l), _ptr(vecs, _lib.c_f32p),
-                                           _ptr(ids, _lib.c_i64p)))
-        return vecs, ids
+    _row = np.float32
 
     def get_vectors(self, l):
         """The list's vectors float32 [size][d], label-sorted."""
         return self._get(l)[0]
 
-    def get_codes(self, l):
-        return self._get(l)[0].view(np.uint8).reshape(-1)
 
-    def get_ids(self, l):
-        return self._get(l)[1]
-
-    imbalance_factor = _InvertedLists.imbalance_factor
-
-
-class IndexIVFFlat:
+class IndexIVFFlat(_IVFIndex):
     """faiss.IndexIVFFlat: IVF over the raw fp32 vectors with exact distances
     (``bench_gpu_1bn.py:575-578`` index keys ending in ``,Flat``; the ``IVF1,Flat``
     ground truth of ``compute_ground_truth.py:311``).  The coarse quantizer is the
-    IndexIVFPQ one; the lists live in HBM only."""
+    IndexIVFPQ one; the lists live in HBM only.  ``search_preassigned`` accepts ``Dq``
+    and ignores it: the scan computes whole distances."""
 
-    _prefix = "ivfpq_ivfflat_"  # the C-ABI family of the handle (IndexIVFScalarQuantizer has its own)
-
-    def _fn(self, name):
-        return getattr(_lib.load(), self._prefix + name)
+    _c = _lib.Family("ivfpq_ivfflat_")
+    _faiss_name = "IndexIVFFlat"
 
     def __init__(self, quantizer, d, nlist, metric=METRIC_L2, device=None):
-        self.d = int(d)
-        self.nlist = int(nlist)
-        self.metric_type = metric
-        self.device = _default_device() if device is None else int(device)
-        if quantizer is None:
-            quantizer = (IndexFlatIP if metric == METRIC_INNER_PRODUCT else IndexFlatL2)(d, self.device)
-        self.quantizer = quantizer
-        self.parallel_mode = 0
-        self.verbose = False
-        self.niter_coarse = 25
-        self.seed = 1234
-        h = _lib.c_handle()
-        _lib.check(self._fn("create")(self.d, self.nlist, metric, self.device, ctypes.byref(h)))
-        self._h = h
+        _IVFIndex.__init__(self, quantizer, d, nlist, metric, device)
+        self._create(self.d, self.nlist, metric, self.device)
         self.invlists = _FlatInvertedLists(self)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            getattr(_lib._lib, self._prefix + "free")(h)
-            self._h = None
-
-    @property
-    def ntotal(self):
-        return int(self._fn("ntotal")(self._h))
-
-    @property
-    def is_trained(self):
-        return bool(self._fn("is_trained")(self._h))
-
-    @property
-    def nprobe(self):
-        return int(self._fn("get_nprobe")(self._h))
-
-    @nprobe.setter
-    def nprobe(self, p):
-        _lib.check(self._fn("set_nprobe")(self._h, int(p)))
 
     @property
     def code_size(self):
         return 4 * self.d
 
-    def centroids(self):
-        c = np.empty((self.nlist, self.d), np.float32)
-        _lib.check(self._fn("get_centroids")(self._h, _ptr(c, _lib.c_f32p)))
-        return c
-
-    _sync_quantizer = IndexIVFPQ._sync_quantizer
-
-    # ----------------------------------------------------------- build path
     def train(self, x):
         x = _f32(x, self.d)
-        _lib.check(self._fn("train")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), self.niter_coarse,
-                                     self.seed))
+        _lib.check(self._c.train(self._h, x.shape[0], _ptr(x), self.niter_coarse, self.seed))
         self._sync_quantizer()
 
     def set_trained(self, centroids):
         """Install trained coarse centroids [nlist][d]."""
         c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
-        _lib.check(self._fn("set_trained")(self._h, _ptr(c, _lib.c_f32p)))
+        _lib.check(self._c.set_trained(self._h, _ptr(c)))
         self._sync_quantizer()
 
-    def add(self, x):
-        x = _f32(x, self.d)
-        _lib.check(self._fn("add")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), None))
-
-    def add_with_ids(self, x, ids):
-        x = _f32(x, self.d)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        if ids.shape[0] != x.shape[0]:
-            raise RuntimeError("ids and x have different lengths")
-        _lib.check(self._fn("add")(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(ids, _lib.c_i64p)))
-
-    def reset(self):
-        _lib.check(self._fn("reset")(self._h))
-
-    # ------------------------------------------------------------ search path
-    _check_k = IndexIVFPQ._check_k
-    _check_dev = IndexIVFPQ._check_dev
-    _dev_outputs = IndexIVFPQ._dev_outputs
-    _stream = IndexIVFPQ._stream
-    search_preassigned = IndexIVFPQ.search_preassigned
-
-    def search(self, x, k):
-        x = _f32(x, self.d)
-        self._check_k(k)
-        n = x.shape[0]
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(self._fn("search")(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                      _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    def _search_preassigned(self, x, k, Iq, Dq=None):
-        """Dq is accepted and ignored: the scan computes whole distances."""
-        x = _f32(np.asarray(x).reshape(-1, self.d), self.d)
-        self._check_k(k)
-        n = x.shape[0]
-        Iq = np.ascontiguousarray(Iq, np.int64).reshape(n, -1)
-        if Iq.shape[1] != self.nprobe:
-            raise RuntimeError(f"Iq must have nprobe={self.nprobe} columns, got {Iq.shape[1]}")
-        Dqp = None
-        if Dq is not None:
-            Dq = np.ascontiguousarray(Dq, np.float32).reshape(Iq.shape)
-            Dqp = _ptr(Dq, _lib.c_f32p)
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(self._fn("search_preassigned")(self._h, n, _ptr(x, _lib.c_f32p), int(k),
-                                                  _ptr(Iq, _lib.c_i64p), Dqp, _ptr(D, _lib.c_f32p),
-                                                  _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    # ------------------------------------------------- device (torch) entry points
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
-        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
-        import torch
-
-        self._check_k(k)
-        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
-        D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(self._fn("search_device")(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                             I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
-
-    def search_preassigned_device(self, x, k, Iq, Dq=None, D=None, I=None, stream=None):
-        """search_preassigned with HBM-resident inputs (Dq is checked and ignored)."""
-        import torch
-
-        self._check_k(k)
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        self._check_dev(Iq, "Iq", torch.int64, (n, self.nprobe))
-        if Dq is not None:
-            self._check_dev(Dq, "Dq", torch.float32, (n, self.nprobe))
-        D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(self._fn("search_preassigned_device")(
-            self._h, n, x.data_ptr(), int(k), Iq.data_ptr(), Dq.data_ptr() if Dq is not None else None,
-            D.data_ptr(), I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
-
-    def add_device(self, x, ids=None, stream=None):
-        """add / add_with_ids with the vectors already in HBM (torch float32 CUDA
-        tensor [n, d]; ids: int64 CUDA tensor [n] or None for sequential ids);
-        returns once the vectors are in place."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        if ids is not None:
-            self._check_dev(ids, "ids", torch.int64, (n,))
-        _lib.check(self._fn("add_device")(self._h, n, x.data_ptr(),
-                                          ids.data_ptr() if ids is not None else None,
-                                          ctypes.c_void_p(self._stream(x, stream))))
+    def _faiss_bytes(self):
+        inv = self.invlists
+        lists = [(inv.get_ids(l), inv.get_vectors(l)) for l in range(self.nlist)]
+        return faiss_io.serialize_ivfflat(self.d, self.nlist, self.nprobe, self.metric_type, self.centroids(), lists)
 
 
 class ScalarQuantizer:
@@ -1235,113 +805,80 @@ class ScalarQuantizer:
 
     @property
     def trained(self):
-        """float32: [vmin (d), vdiff (d)] (QT_8bit), [vmin, vdiff] (QT_8bit_uniform), empty (QT_fp16)."""
-        return self._owner._trained()
+        """float32: [vmin (d), vdiff (d)] (QT_8bit), [vmin, vdiff] (QT_8bit_uniform), empty (QT_fp16);
+        read from the owner's family: one call for the length, one for the values."""
+        ix = self._owner
+        if not ix.is_trained:
+            return np.zeros(0, np.float32)
+        n = ctypes.c_int64()
+        _lib.check(ix._c.get_trained(ix._h, None, ctypes.byref(n)))
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            _lib.check(ix._c.get_trained(ix._h, _ptr(out), None))
+        return out
 
 
 _SQ_NAMES = {v: n for n, v in vars(ScalarQuantizer).items() if n.startswith("QT_")}
 
 
-class IndexScalarQuantizer:
+class IndexScalarQuantizer(_HandleIndex):
     """faiss.IndexScalarQuantizer(d, qtype, metric) for QT_fp16, QT_8bit and QT_8bit_uniform
     (beir faiss_search.py:415-459 SQFaissSearch): every code is decoded and compared with
     every query in one fused scan.  Labels are positions: there is no id map, as in Faiss."""
 
+    _c = _lib.Family("ivfpq_sq_")
+    _faiss_name = "IndexScalarQuantizer"
+
     def __init__(self, d, qtype, metric=METRIC_L2, device=None):
-        self.d = int(d)
+        _HandleIndex.__init__(self, d, metric, device)
         self.qtype = int(qtype)
-        self.metric_type = metric
-        self.device = _default_device() if device is None else int(device)
-        self.verbose = False
-        h = _lib.c_handle()
-        _lib.check(_lib.load().ivfpq_sq_create(self.d, self.qtype, metric, self.device, ctypes.byref(h)))
-        self._h = h
+        self._create(self.d, self.qtype, metric, self.device)
         cs = ctypes.c_int()
-        _lib.check(_lib.load().ivfpq_sq_get_dims(h, None, None, None, ctypes.byref(cs)))
+        _lib.check(self._c.get_dims(self._h, None, None, None, ctypes.byref(cs)))
         self.code_size = cs.value
         self.sq = ScalarQuantizer(self)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_sq_free(h)
-            self._h = None
-
-    @property
-    def ntotal(self):
-        return int(_lib.load().ivfpq_sq_ntotal(self._h))
-
-    @property
-    def is_trained(self):
-        return bool(_lib.load().ivfpq_sq_is_trained(self._h))
-
     def sa_code_size(self):
         return self.code_size
-
-    def _trained(self):
-        if not self.is_trained:
-            return np.zeros(0, np.float32)
-        n = ctypes.c_int64()
-        _lib.check(_lib.load().ivfpq_sq_get_trained(self._h, None, ctypes.byref(n)))
-        out = np.empty(n.value, np.float32)
-        if n.value:
-            _lib.check(_lib.load().ivfpq_sq_get_trained(self._h, _ptr(out, _lib.c_f32p), None))
-        return out
-
-    def _codes(self, i0, n):
-        out = np.empty((n, self.code_size), np.uint8)
-        _lib.check(_lib.load().ivfpq_sq_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
-        return out
 
     @property
     def codes(self):
         """uint8 [ntotal * code_size] (faiss.vector_to_array(index.codes))."""
         return self._codes(0, self.ntotal).reshape(-1)
 
+    def _code_rows(self, codes):
+        codes = np.ascontiguousarray(codes, np.uint8)
+        if codes.size % self.code_size:
+            raise RuntimeError(f"codes must hold whole rows of {self.code_size} bytes")
+        return codes.reshape(-1, self.code_size)
+
     # ----------------------------------------------------------- build path
     def train(self, x):
         x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_sq_train(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
+        _lib.check(self._c.train(self._h, x.shape[0], _ptr(x)))
 
     def set_trained(self, trained):
         """Install ``sq.trained`` (see ScalarQuantizer.trained)."""
         t = np.ascontiguousarray(trained, np.float32).reshape(-1)
-        _lib.check(_lib.load().ivfpq_sq_set_trained(self._h, _ptr(t, _lib.c_f32p), t.size))
-
-    def add(self, x):
-        x = _f32(x, self.d)
-        _lib.check(_lib.load().ivfpq_sq_add(self._h, x.shape[0], _ptr(x, _lib.c_f32p)))
-
-    def add_with_ids(self, x, ids):
-        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss Index::add_with_ids
+        _lib.check(self._c.set_trained(self._h, _ptr(t), t.size))
 
     def add_codes(self, codes):
         """Append precomputed codes uint8 [n][code_size]."""
-        codes = np.ascontiguousarray(codes, np.uint8)
-        if codes.size % self.code_size:
-            raise RuntimeError(f"codes must hold whole rows of {self.code_size} bytes")
-        codes = codes.reshape(-1, self.code_size)
-        _lib.check(_lib.load().ivfpq_sq_add_codes(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p)))
-
-    def reset(self):
-        _lib.check(_lib.load().ivfpq_sq_reset(self._h))
+        codes = self._code_rows(codes)
+        _lib.check(self._c.add_codes(self._h, codes.shape[0], _ptr(codes)))
 
     def sa_encode(self, x):
         """float32 [n][d] -> uint8 [n][code_size], encoded on the GPU."""
         x = _f32(x, self.d)
         out = np.empty((x.shape[0], self.code_size), np.uint8)
-        _lib.check(_lib.load().ivfpq_sq_encode(self._h, x.shape[0], _ptr(x, _lib.c_f32p), _ptr(out, _lib.c_u8p)))
+        _lib.check(self._c.encode(self._h, x.shape[0], _ptr(x), _ptr(out)))
         return out
 
     def sa_decode(self, codes):
         """uint8 [n][code_size] -> float32 [n][d], decoded on the GPU."""
-        codes = np.ascontiguousarray(codes, np.uint8)
-        if codes.size % self.code_size:
-            raise RuntimeError(f"codes must hold whole rows of {self.code_size} bytes")
-        codes = codes.reshape(-1, self.code_size)
+        codes = self._code_rows(codes)
         out = np.empty((codes.shape[0], self.d), np.float32)
-        _lib.check(_lib.load().ivfpq_sq_decode(self._h, codes.shape[0], _ptr(codes, _lib.c_u8p),
-                                               _ptr(out, _lib.c_f32p)))
+        _lib.check(self._c.decode(self._h, codes.shape[0], _ptr(codes), _ptr(out)))
         return out
 
     def reconstruct_n(self, i0, n):
@@ -1350,70 +887,14 @@ class IndexScalarQuantizer:
     def reconstruct(self, i):
         return self.reconstruct_n(i, 1)[0]
 
-    # ------------------------------------------------------------ search path
-    _check_k = IndexIVFPQ._check_k
-    _check_dev = IndexIVFPQ._check_dev
-    _dev_outputs = IndexIVFPQ._dev_outputs
-    _stream = IndexIVFPQ._stream
-
-    def search(self, x, k):
-        x = _f32(x, self.d)
-        self._check_k(k)
-        n = x.shape[0]
-        D = np.empty((n, k), np.float32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_sq_search(self._h, n, _ptr(x, _lib.c_f32p), int(k), _ptr(D, _lib.c_f32p),
-                                               _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with the queries resident in HBM (torch float32 CUDA tensor [n, d]);
-        returns torch (D, I), launched on ``stream`` (default: torch's current stream)."""
-        import torch
-
-        self._check_k(k)
-        self._check_dev(x, "x", torch.float32, (x.shape[0] if x.dim() == 2 else -1, self.d))
-        D, I = self._dev_outputs(x, k, D, I)
-        _lib.check(_lib.load().ivfpq_sq_search_device(self._h, x.shape[0], x.data_ptr(), int(k), D.data_ptr(),
-                                                      I.data_ptr(), ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
-
-    def add_device(self, x, stream=None):
-        """add with the vectors already in HBM; returns once the codes are in place."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.float32, (n, self.d))
-        _lib.check(_lib.load().ivfpq_sq_add_device(self._h, n, x.data_ptr(),
-                                                   ctypes.c_void_p(self._stream(x, stream))))
+    def _faiss_bytes(self):
+        return faiss_io.serialize_sq(self.d, self.qtype, self.metric_type, self.sq.trained,
+                                     self._codes(0, self.ntotal))
 
 
-class _CodeInvertedLists:
-    """index.invlists of an IndexIVFScalarQuantizer (faiss ArrayInvertedLists read API): the
-    codes of a list are its rows' scalar-quantizer codes, ``code_size`` bytes each."""
-
-    def __init__(self, owner):
-        self._o = owner
-
-    nlist = _FlatInvertedLists.nlist
-    list_sizes = _FlatInvertedLists.list_sizes
-    list_size = _FlatInvertedLists.list_size
-    get_ids = _FlatInvertedLists.get_ids
-    imbalance_factor = _InvertedLists.imbalance_factor
-
-    @property
-    def code_size(self):
-        return self._o.code_size
-
-    def _get(self, l):
-        n = self.list_size(l)
-        codes = np.empty((n, self._o.code_size), np.uint8)
-        ids = np.empty(n, np.int64)
-        _lib.check(self._o._fn("get_list")(self._o._h, int(l), _ptr(codes, _lib.c_u8p), _ptr(ids, _lib.c_i64p)))
-        return codes, ids
-
-    def get_codes(self, l):
-        return self._get(l)[0].reshape(-1)
+class _CodeInvertedLists(_ListsView):
+    """index.invlists of an IndexIVFScalarQuantizer: the codes of a list are its rows'
+    scalar-quantizer codes, ``code_size`` bytes each."""
 
 
 class IndexIVFScalarQuantizer(IndexIVFFlat):
@@ -1425,28 +906,16 @@ class IndexIVFScalarQuantizer(IndexIVFFlat):
     ``bench_gpu_1bn.py``.  Every method of IndexIVFFlat; ``search_preassigned`` reads ``Dq`` for the
     inner product with ``by_residual`` (None: zeros) and ignores it otherwise."""
 
-    _prefix = "ivfpq_ivfsq_"
+    _c = _lib.Family("ivfpq_ivfsq_")
+    _faiss_name = "IndexIVFScalarQuantizer"
 
     def __init__(self, quantizer, d, nlist, qtype, metric=METRIC_L2, by_residual=True, device=None):
-        self.d = int(d)
-        self.nlist = int(nlist)
+        _IVFIndex.__init__(self, quantizer, d, nlist, metric, device)
         self.qtype = int(qtype)
-        self.metric_type = metric
         self.by_residual = bool(by_residual)
-        self.device = _default_device() if device is None else int(device)
-        if quantizer is None:
-            quantizer = (IndexFlatIP if metric == METRIC_INNER_PRODUCT else IndexFlatL2)(d, self.device)
-        self.quantizer = quantizer
-        self.parallel_mode = 0
-        self.verbose = False
-        self.niter_coarse = 25
-        self.seed = 1234
-        h = _lib.c_handle()
-        _lib.check(self._fn("create")(self.d, self.nlist, self.qtype, metric, int(self.by_residual), self.device,
-                                      ctypes.byref(h)))
-        self._h = h
+        self._create(self.d, self.nlist, self.qtype, metric, int(self.by_residual), self.device)
         cs = ctypes.c_int()
-        _lib.check(self._fn("get_dims")(h, None, None, None, None, None, ctypes.byref(cs)))
+        _lib.check(self._c.get_dims(self._h, None, None, None, None, None, ctypes.byref(cs)))
         self._code_size = cs.value
         self.sq = ScalarQuantizer(self)
         self.invlists = _CodeInvertedLists(self)
@@ -1455,86 +924,55 @@ class IndexIVFScalarQuantizer(IndexIVFFlat):
     def code_size(self):
         return self._code_size
 
-    def _trained(self):
-        if not self.is_trained:
-            return np.zeros(0, np.float32)
-        n = ctypes.c_int64()
-        _lib.check(self._fn("get_trained")(self._h, None, ctypes.byref(n)))
-        out = np.empty(n.value, np.float32)
-        if n.value:
-            _lib.check(self._fn("get_trained")(self._h, _ptr(out, _lib.c_f32p), None))
-        return out
-
     def set_trained(self, centroids, sq_trained=()):
         """Install trained coarse centroids [nlist][d] and ``sq.trained`` (see ScalarQuantizer.trained)."""
         c = _f32(np.asarray(centroids).reshape(self.nlist, self.d), self.d, "centroids")
         t = np.ascontiguousarray(sq_trained, np.float32).reshape(-1)
-        _lib.check(self._fn("set_trained")(self._h, _ptr(c, _lib.c_f32p), _ptr(t, _lib.c_f32p), t.size))
+        _lib.check(self._c.set_trained(self._h, _ptr(c), _ptr(t), t.size))
         self._sync_quantizer()
 
     def add_codes(self, list_no, codes, ids=None):
         """Append precomputed codes uint8 [n][code_size] to the lists ``list_no`` [n] with labels
         ``ids`` (None: sequential), as read from an index file."""
-        list_no = np.ascontiguousarray(list_no, np.int64).reshape(-1)
-        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.code_size)
-        n = list_no.shape[0]
-        if codes.shape[0] != n:
-            raise RuntimeError("codes and list_no have different lengths")
-        idp = None
-        if ids is not None:
-            ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-            if ids.shape[0] != n:
-                raise RuntimeError("ids and list_no have different lengths")
-            idp = _ptr(ids, _lib.c_i64p)
-        _lib.check(self._fn("add_codes")(self._h, n, _ptr(list_no, _lib.c_i64p), _ptr(codes, _lib.c_u8p), idp))
+        self._add_listed(self._c.add_codes, list_no, codes, ids)
+
+    def _faiss_bytes(self):
+        lists = [self.invlists._get(l)[::-1] for l in range(self.nlist)]
+        return faiss_io.serialize_ivfsq(self.d, self.nlist, self.nprobe, self.qtype, self.metric_type,
+                                        self.by_residual, self.centroids(), self.sq.trained, lists)
 
 
-class IndexBinaryFlat:
+class IndexBinaryFlat(_HandleIndex):
     """faiss.IndexBinaryFlat(d): exact Hamming search over uint8 codes of ``d`` bits (beir
     faiss_search.py BinaryFaissSearch builds ``IndexBinaryFlat(dim * 8)``).  ``search`` returns
     ``D`` int32 and ``I`` int64: per query the k smallest (hamming, label) pairs ascending, ties
     by label, padded with (2147483647, -1).  The distances equal Faiss's for either value of
     ``use_heap``; the labels equal ``use_heap = False`` (hammings_knn_mc, first-seen ids per
     distance), while Faiss's default heap path may keep other ties at the k-th distance and
-    orders equal distances arbitrarily.  Labels are positions: there is no id map."""
+    orders equal distances arbitrarily.  Labels are positions: there is no id map.  Queries and
+    rows are uint8 [n, code_size], on the host and in HBM (``search_device``, ``add_device``)."""
+
+    _c = _lib.Family("ivfpq_bin_")
+    _dist = "int32"
+    is_trained = True
 
     def __init__(self, d, device=None):
-        self.d = int(d)
-        self.metric_type = METRIC_L2  # as Faiss's IndexBinary
-        self.device = _default_device() if device is None else int(device)
-        self.verbose = False
+        _HandleIndex.__init__(self, d, METRIC_L2, device)  # the metric as Faiss's IndexBinary
         self.use_heap = True          # accepted, no effect: see the class comment
         self.query_batch_size = 32    # accepted, no effect
-        h = _lib.c_handle()
-        _lib.check(_lib.load().ivfpq_bin_create(self.d, self.device, ctypes.byref(h)))
-        self._h = h
+        self._create(self.d, self.device)
         self.code_size = self.d // 8
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.ivfpq_bin_free(h)
-            self._h = None
-
-    @property
-    def ntotal(self):
-        return int(_lib.load().ivfpq_bin_ntotal(self._h))
-
-    @property
-    def is_trained(self):
-        return True
-
-    def _u8(self, x, name="x"):
+    def _host_rows(self, x):
         a = np.ascontiguousarray(x)
         if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != self.code_size:
-            raise RuntimeError(f"{name} must be a uint8 matrix with {self.code_size} columns, got "
-                               f"{a.dtype} {a.shape}")
+            raise RuntimeError(f"x must be a uint8 matrix with {self.code_size} columns, got {a.dtype} {a.shape}")
         return a
 
-    def _codes(self, i0, n):
-        out = np.empty((n, self.code_size), np.uint8)
-        _lib.check(_lib.load().ivfpq_bin_get_codes(self._h, int(i0), int(n), _ptr(out, _lib.c_u8p)))
-        return out
+    def _dev_row(self):
+        import torch
+
+        return torch.uint8, self.code_size
 
     @property
     def xb(self):
@@ -1544,62 +982,11 @@ class IndexBinaryFlat:
     def train(self, x):
         pass
 
-    def add(self, x):
-        x = self._u8(x)
-        _lib.check(_lib.load().ivfpq_bin_add(self._h, x.shape[0], _ptr(x, _lib.c_u8p)))
-
-    def add_with_ids(self, x, ids):
-        raise RuntimeError("add_with_ids not implemented for this type of index")  # Faiss IndexBinary::add_with_ids
-
-    def reset(self):
-        _lib.check(_lib.load().ivfpq_bin_reset(self._h))
-
     def reconstruct_n(self, i0, n):
         return self._codes(i0, n)
 
     def reconstruct(self, i):
         return self._codes(i, 1)[0]
-
-    _check_k = IndexIVFPQ._check_k
-    _check_dev = IndexIVFPQ._check_dev
-    _stream = IndexIVFPQ._stream
-
-    def search(self, x, k):
-        x = self._u8(x)
-        self._check_k(k)
-        n = x.shape[0]
-        D = np.empty((n, k), np.int32)
-        I = np.empty((n, k), np.int64)
-        _lib.check(_lib.load().ivfpq_bin_search(self._h, n, _ptr(x, _lib.c_u8p), int(k), _ptr(D, _lib.c_i32p),
-                                                _ptr(I, _lib.c_i64p)))
-        return D, I
-
-    def search_device(self, x, k, D=None, I=None, stream=None):
-        """Search with the queries resident in HBM (torch uint8 CUDA tensor [n, code_size]);
-        returns torch (D int32, I int64), launched on ``stream`` (default: torch's current stream)."""
-        import torch
-
-        self._check_k(k)
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.uint8, (n, self.code_size))
-        if D is None:
-            D = torch.empty((n, k), dtype=torch.int32, device=x.device)
-        if I is None:
-            I = torch.empty((n, k), dtype=torch.int64, device=x.device)
-        self._check_dev(D, "D", torch.int32, (n, k))
-        self._check_dev(I, "I", torch.int64, (n, k))
-        _lib.check(_lib.load().ivfpq_bin_search_device(self._h, n, x.data_ptr(), int(k), D.data_ptr(), I.data_ptr(),
-                                                       ctypes.c_void_p(self._stream(x, stream))))
-        return D, I
-
-    def add_device(self, x, stream=None):
-        """add with the codes already in HBM; returns once they are in place."""
-        import torch
-
-        n = x.shape[0] if x.dim() == 2 else -1
-        self._check_dev(x, "x", torch.uint8, (n, self.code_size))
-        _lib.check(_lib.load().ivfpq_bin_add_device(self._h, n, x.data_ptr(),
-                                                    ctypes.c_void_p(self._stream(x, stream))))
 
 
 def decode_pq(codebook, codes):
@@ -1791,112 +1178,52 @@ class ParameterSpace:
             self.set_index_parameter(index, name.strip(), float(value))
 
 
-def _ivfpq_bytes(index):
-    inv = index.invlists
-    lists = [(inv.get_ids(l), inv.get_codes(l).reshape(-1, index.code_size)) for l in range(index.nlist)]
-    return faiss_io.serialize_ivfpq(index.d, index.nlist, index.nprobe, index.M, index.nbits, index.metric_type,
-                                    index.centroids(), index.codebook(), lists)
-
-
-def _pq_bytes(index):
-    if not index.is_trained:
-        raise RuntimeError("IndexPQ is written once trained")
-    return faiss_io.serialize_pq(index.d, index.M, index.nbits, index.metric_type, index.codebook(),
-                                 index._codes(0, index.ntotal))
-
-
-def _ivfflat_bytes(index):
-    if not index.is_trained:
-        raise RuntimeError("IndexIVFFlat is written once trained")
-    inv = index.invlists
-    lists = [(inv.get_ids(l), inv.get_vectors(l)) for l in range(index.nlist)]
-    return faiss_io.serialize_ivfflat(index.d, index.nlist, index.nprobe, index.metric_type, index.centroids(), lists)
-
-
-def _sq_bytes(index):
-    if not index.is_trained:
-        raise RuntimeError("IndexScalarQuantizer is written once trained")
-    return faiss_io.serialize_sq(index.d, index.qtype, index.metric_type, index.sq.trained,
-                                 index._codes(0, index.ntotal))
-
-
-def _ivfsq_bytes(index):
-    if not index.is_trained:
-        raise RuntimeError("IndexIVFScalarQuantizer is written once trained")
-    inv = index.invlists
-    lists = [inv._get(l)[::-1] for l in range(index.nlist)]
-    return faiss_io.serialize_ivfsq(index.d, index.nlist, index.nprobe, index.qtype, index.metric_type,
-                                    index.by_residual, index.centroids(), index.sq.trained, lists)
-
-
-def _flat_bytes(index):
-    return faiss_io.serialize_flat(index.d, index.metric_type, index.xb.reshape(-1, index.d))
-
-
-def _sub_bytes(index):
-    if isinstance(index, IndexFlat):
-        return _flat_bytes(index)
-    if isinstance(index, IndexIVFScalarQuantizer):
-        return _ivfsq_bytes(index)
-    if isinstance(index, IndexIVFFlat):
-        return _ivfflat_bytes(index)
-    if isinstance(index, IndexScalarQuantizer):
-        return _sq_bytes(index)
-    return _pq_bytes(index) if isinstance(index, IndexPQ) else _ivfpq_bytes(index)
-
-
 def write_index(index, path, fmt="faiss"):
     """Persist ``index``.  fmt "faiss": the Faiss 1.7.1 IndexIVFPQ / IndexPQ /
     IndexIVFFlat / IndexIVFScalarQuantizer / IndexScalarQuantizer / IndexFlat / IndexPreTransform binary layout (``faiss.read_index`` loads it; faiss_io.py);
     "native": this library's CHIVFPQ1 image (also keeps untrained indexes; IVF-PQ only)."""
     from .transform import IndexPreTransform, _transform_bytes
 
+    # every class that has a Faiss layout states it: _faiss_bytes() and, for the messages, _faiss_name
     if isinstance(index, IndexPreTransform):
         if fmt != "faiss" or not index.is_trained:
             raise RuntimeError("IndexPreTransform is written in the Faiss layout once trained")
         chain = [_transform_bytes(t) for t in index.chain]
-        buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, _sub_bytes(index.index),
+        buf = faiss_io.serialize_pretransform(index.d, index.metric_type, chain, index.index._faiss_bytes(),
                                               index.ntotal)
-    elif isinstance(index, IndexFlat):
+    elif not isinstance(index, IndexIVFPQ):
         if fmt != "faiss":
-            raise RuntimeError("IndexFlat is written in the Faiss layout")
-        buf = _flat_bytes(index)
-    elif isinstance(index, IndexPQ):
-        if fmt != "faiss":
-            raise RuntimeError("IndexPQ is written in the Faiss layout")
-        buf = _pq_bytes(index)
-    elif isinstance(index, IndexScalarQuantizer):
-        if fmt != "faiss":
-            raise RuntimeError("IndexScalarQuantizer is written in the Faiss layout")
-        buf = _sq_bytes(index)
-    elif isinstance(index, IndexIVFScalarQuantizer):
-        if fmt != "faiss":
-            raise RuntimeError("IndexIVFScalarQuantizer is written in the Faiss layout")
-        buf = _ivfsq_bytes(index)
-    elif isinstance(index, IndexIVFFlat):
-        if fmt != "faiss":
-            raise RuntimeError("IndexIVFFlat is written in the Faiss layout")
-        buf = _ivfflat_bytes(index)
+            raise RuntimeError(f"{index._faiss_name} is written in the Faiss layout")
+        if not index.is_trained:
+            raise RuntimeError(f"{index._faiss_name} is written once trained")
+        buf = index._faiss_bytes()
     elif fmt == "native" or not index.is_trained:
-        _lib.check(_lib.load().ivfpq_save(index._h, str(path).encode()))
+        _lib.check(index._c.save(index._h, str(path).encode()))
         return
     elif fmt != "faiss":
         raise RuntimeError(f"unknown index file format {fmt!r}")
     else:
-        buf = _ivfpq_bytes(index)
+        buf = index._faiss_bytes()
     with open(path, "wb") as f:
         f.write(buf)
+
+
+def _listed(lists):
+    """The non-empty lists [(ids, rows)] of a parsed file as one (list_no, rows, ids), or None."""
+    nonempty = [(l, ids, rows) for l, (ids, rows) in enumerate(lists) if len(ids)]
+    if not nonempty:
+        return None
+    return (np.concatenate([np.full(len(ids), l, np.int64) for l, ids, _ in nonempty]),
+            np.concatenate([rows for _, _, rows in nonempty]), np.concatenate([ids for _, ids, _ in nonempty]))
 
 
 def _ivfpq_from_dict(z, device):
     idx = IndexIVFPQ(None, z["d"], z["nlist"], z["M"], z["nbits"], z["metric"], device)
     if z["is_trained"]:
         idx.set_trained(z["centroids"], z["codebook"])
-        nonempty = [(l, ids, codes) for l, (ids, codes) in enumerate(z["lists"]) if len(ids)]
-        if nonempty:
-            idx.add_preencoded(np.concatenate([np.full(len(ids), l, np.int64) for l, ids, _ in nonempty]),
-                               np.concatenate([codes for _, _, codes in nonempty]),
-                               np.concatenate([ids for _, ids, _ in nonempty]))
+        listed = _listed(z["lists"])
+        if listed:
+            idx.add_preencoded(*listed)
     idx.nprobe = max(1, min(int(z["nprobe"]), z["nlist"]))
     return idx
 
@@ -1916,9 +1243,9 @@ def _ivfflat_from_dict(z, device):
     idx = IndexIVFFlat(None, z["d"], z["nlist"], z["metric"], device)
     if z["is_trained"]:
         idx.set_trained(z["centroids"])
-        nonempty = [(ids, vecs) for ids, vecs in z["lists"] if len(ids)]
-        if nonempty:
-            idx.add_with_ids(np.concatenate([v for _, v in nonempty]), np.concatenate([i for i, _ in nonempty]))
+        listed = _listed(z["lists"])
+        if listed:
+            idx.add_with_ids(listed[1], listed[2])
     idx.nprobe = max(1, min(int(z["nprobe"]), z["nlist"]))
     return idx
 
@@ -1929,11 +1256,9 @@ def _ivfsq_from_dict(z, device):
     idx = IndexIVFScalarQuantizer(None, z["d"], z["nlist"], z["qtype"], z["metric"], z["by_residual"], device)
     if z["is_trained"]:
         idx.set_trained(z["centroids"], z["trained"])
-        nonempty = [(l, ids, codes) for l, (ids, codes) in enumerate(z["lists"]) if len(ids)]
-        if nonempty:
-            idx.add_codes(np.concatenate([np.full(len(ids), l, np.int64) for l, ids, _ in nonempty]),
-                          np.concatenate([codes for _, _, codes in nonempty]),
-                          np.concatenate([ids for _, ids, _ in nonempty]))
+        listed = _listed(z["lists"])
+        if listed:
+            idx.add_codes(*listed)
     idx.nprobe = max(1, min(int(z["nprobe"]), z["nlist"]))
     return idx
 
@@ -1955,16 +1280,8 @@ def _flat_from_dict(z, device):
     return idx
 
 
-def _index_from_dict(z, device):
-    if z["kind"] == "flat":
-        return _flat_from_dict(z, device)
-    if z["kind"] == "ivfflat":
-        return _ivfflat_from_dict(z, device)
-    if z["kind"] == "ivfsq":
-        return _ivfsq_from_dict(z, device)
-    if z["kind"] == "sq":
-        return _sq_from_dict(z, device)
-    return _pq_from_dict(z, device) if z["kind"] == "pq" else _ivfpq_from_dict(z, device)
+_FROM_DICT = {"flat": _flat_from_dict, "ivfflat": _ivfflat_from_dict, "ivfsq": _ivfsq_from_dict, "sq": _sq_from_dict,
+              "pq": _pq_from_dict, "ivfpq": _ivfpq_from_dict}  # by faiss_io.parse_index's "kind"
 
 
 def read_index(path, device=None):
@@ -1979,10 +1296,11 @@ def read_index(path, device=None):
         with open(path, "rb") as f:
             z = faiss_io.parse_index(f.read())
         if z["kind"] != "pretransform":
-            return _index_from_dict(z, device)
+            return _FROM_DICT[z["kind"]](z, device)
         from .transform import IndexPreTransform, _linear_from_dict
 
-        return IndexPreTransform([_linear_from_dict(t) for t in z["chain"]], _index_from_dict(z["index"], device))
+        sub = z["index"]
+        return IndexPreTransform([_linear_from_dict(t) for t in z["chain"]], _FROM_DICT[sub["kind"]](sub, device))
     h = _lib.c_handle()
     L = _lib.load()
     _lib.check(L.ivfpq_load(str(path).encode(), device, ctypes.byref(h)))

@@ -1842,6 +1842,94 @@ __device__ __forceinline__ void setc(float4& o, int g, float x) {
   if (g == 0) o.x = x; else if (g == 1) o.y = x; else if (g == 2) o.z = x; else o.w = x;
 }
 
+// ------------------------------------------------ LUT stores of the table build
+// A thread of the build holds four consecutive j of a table row and stores them as four
+// LUT vectors V (G floats: 16, 8 or 4 bytes) at slots 4 v + c, c = 0..3.  Stored in the
+// order c = 0, 1, 2, 3 the lanes of one store are 4 sizeof(V) apart: an LDS store is served
+// in aligned groups of 128 / sizeof(V) lanes, a group's lanes cover 128 bytes (32 banks)
+// when their slots differ mod the group size, and at that stride they fall on a quarter of
+// the banks, four deep.  Rotated, lane L stores component (s + r) & 3 in step s, with
+// r = (L / (group / 4)) & 3: the same slots, each written once with the same value, and
+// every step of every group on 32 distinct banks.
+// the rotation of a lane; grp: lanes per store group (8, 16, 32 for 16-, 8-, 4-byte stores)
+__host__ __device__ constexpr int lut_store_rot(int lane, int grp) { return (lane / (grp / 4)) & 3; }
+// the component a lane stores in step s
+__host__ __device__ constexpr int lut_store_comp(int s, int lane, int grp) { return (s + lut_store_rot(lane, grp)) & 3; }
+// the component that the two select stages of lut_store4 leave in u[s] at rotation r
+__host__ __device__ constexpr int lut_store_sel(int s, int r) {
+  const int s2 = (r & 2) ? (s + 2) & 3 : s;  // u[s] = t[s2]
+  return (r & 1) ? (s2 + 1) & 3 : s2;        // t[s2] = o[...]
+}
+// every step of every aligned lane group on distinct bank classes (slot mod group size)
+constexpr bool lut_store_banks_ok(int grp) {
+  for (int s = 0; s < 4; s++)
+    for (int l0 = 0; l0 < 64; l0 += grp) {
+      unsigned seen = 0;
+      for (int l = l0; l < l0 + grp; l++) {
+        const unsigned b = 1u << ((4 * l + lut_store_comp(s, l, grp)) % grp);
+        if (seen & b) return false;
+        seen |= b;
+      }
+    }
+  return true;
+}
+// every lane's four steps cover the components 0..3 once, and the selects deliver them
+constexpr bool lut_store_covers(int grp) {
+  for (int l = 0; l < 64; l++) {
+    unsigned seen = 0;
+    for (int s = 0; s < 4; s++) {
+      const int c = lut_store_comp(s, l, grp);
+      if (c != lut_store_sel(s, lut_store_rot(l, grp))) return false;
+      seen |= 1u << c;
+    }
+    if (seen != 0xfu) return false;
+  }
+  return true;
+}
+static_assert(lut_store_banks_ok(8) && lut_store_banks_ok(16) && lut_store_banks_ok(32),
+              "LUT stores: a step of a lane group falls twice on one bank");
+static_assert(lut_store_covers(8) && lut_store_covers(16) && lut_store_covers(32),
+              "LUT stores: a lane's four steps are not the components 0..3 once each");
+// How k_scan_lean builds its LUT (profiles/lut_store_banks.md; all three give the same LUT):
+//   SCAN_LUT_DWORD 1 (shipped, the split forms): thread t holds column j = t of every row of
+//     the pass, loaded one dword per row and table, and stores lut[m][t]: lanes 16 bytes
+//     apart, conflict-free without a transpose.  C2 step -1.5 % against the row form.
+//   SCAN_LUT_DWORD 0: thread t holds four consecutive j of a row (16-byte loads) and stores
+//     them through lut_store4, in the order c = 0..3 (SCAN_LUT_ROTATE 0, the scan before, and
+//     what the one-pass forms keep) or rotated (SCAN_LUT_ROTATE 1: no conflict cycles either,
+//     but 32 v_cndmask per row vector; C2 step +1.2 %, not shipped).
+#ifndef SCAN_LUT_DWORD
+#define SCAN_LUT_DWORD 1
+#endif
+#ifndef SCAN_LUT_ROTATE
+#define SCAN_LUT_ROTATE 0
+#endif
+// o[c] to p[c], c = 0..3 (p: slot 4 v of the LUT), rotated by the lane.  The rotation is two
+// select stages on named registers, 2 G v_cndmask per vector: a component picked by a run-time
+// index would go through private memory.
+template <bool ROT, typename V, int G>
+__device__ __forceinline__ void lut_store4(V* p, const V (&o)[4], int lane) {
+  if constexpr (ROT) {
+    constexpr int GRP = 128 / (int)sizeof(V);
+    const int r = lut_store_rot(lane, GRP);
+    const bool r1 = (r & 1) != 0, r2 = (r & 2) != 0;
+    V t[4], u[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+      for (int g = 0; g < G; g++) setc(t[c], g, r1 ? comp(o[(c + 1) & 3], g) : comp(o[c], g));
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+      for (int g = 0; g < G; g++) setc(u[c], g, r2 ? comp(t[(c + 2) & 3], g) : comp(t[c], g));
+#pragma unroll
+    for (int s = 0; s < 4; s++) p[lut_store_comp(s, lane, GRP)] = u[s];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; c++) p[c] = o[c];
+  }
+}
+
 template <int M>
 struct CodeWords {
   uint32_t w[M / 4];
@@ -2712,8 +2800,8 @@ __device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v) {  // lane i <- lan
 // LUT quarters alternate between two 16 KB buffers, pass p + 1's rows are loaded ahead
 // of pass p's gathers, and there is one barrier per pass (FOUR below).
 // REGISTER BUDGET, without scratch in every form:
-//   NP = 2 (shipped): 146 VGPRs of the 168 of three waves per SIMD, 40,000 B of LDS;
-//   NP = 4: 120 VGPRs of the 128 of four waves per SIMD, 40,000 B (of the 40,960 of four per CU).
+//   NP = 2 (shipped): 150 VGPRs of the 168 of three waves per SIMD, 40,000 B of LDS;
+//   NP = 4: 116 VGPRs of the 128 of four waves per SIMD, 40,000 B (of the 40,960 of four per CU).
 // They get there only through opq() below and through readfirstlane on the item's query
 // indices in unpack() (uniform, but computed on the VALU: it.q[] and its copies qix[]
 // otherwise take eight VGPRs across the scan; the two-pass form sat at exactly 168 before).
@@ -2784,6 +2872,9 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
   constexpr bool FOUR = NP == 4;
   static_assert(!FOUR || MH == 4, "lean scan, four passes: one code word per pass");
   constexpr int LB = LUTN / NP;  // float4 per LUT buffer
+  // COL: a thread builds column tid of the pass's MH rows instead of four consecutive j of
+  // NH row vectors (SCAN_LUT_DWORD above; the one-pass forms keep the row vectors)
+  constexpr bool COL = SPLIT && SCAN_LUT_DWORD != 0;
   constexpr bool kPre = kScanPrefetch && !SPLIT;
   __shared__ __attribute__((aligned(16))) float4 lut[(FOUR ? 2 : 1) * LB];  // [buffer][m of the pass][j][g]
   __shared__ int s_next;
@@ -2899,26 +2990,40 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
         reinterpret_cast<const float4*>(ip ? a.T3 + (int64_t)it.q[0] * LUTN : a.T1 + (int64_t)it.l * LUTN);
 #pragma unroll
     for (int e = 0; e < NH; e++) {
-      const int v = (hf * NH + e) * 256 + tid;
+      if constexpr (COL) {  // component c of b1[e] / b3[e][g]: column tid of row 4 e + c of the pass
 #pragma unroll
-      for (int g = 0; g < G; g++) b3[e][g] = reinterpret_cast<const float4*>(a.T3 + (int64_t)it.q[g] * LUTN)[v];
-      b1[e] = T1l[v];
+        for (int c = 0; c < 4; c++) {
+          const int i = (4 * (hf * NH + e) + c) * 256 + tid;
+#pragma unroll
+          for (int g = 0; g < G; g++) setc(b3[e][g], c, (a.T3 + (int64_t)it.q[g] * LUTN)[i]);
+          setc(b1[e], c, reinterpret_cast<const float*>(T1l)[i]);
+        }
+      } else {
+        const int v = (hf * NH + e) * 256 + tid;
+#pragma unroll
+        for (int g = 0; g < G; g++) b3[e][g] = reinterpret_cast<const float4*>(a.T3 + (int64_t)it.q[g] * LUTN)[v];
+        b1[e] = T1l[v];
+      }
     }
   };
   auto store_rows = [&](int buf) __attribute__((always_inline)) {
     const int tid = opq(threadIdx.x);
 #pragma unroll
     for (int e = 0; e < NH; e++) {
-      const int v = e * 256 + tid;
+      float4 o[4];
 #pragma unroll
       for (int c = 0; c < 4; c++) {
-        float4 o;
 #pragma unroll
         for (int g = 0; g < G; g++) {
           const float x3 = comp(b3[e][g], c);
-          setc(o, g, ip ? -x3 : __builtin_fmaf(x3, -2.0f, comp(b1[e], c)));  // (oracle: one rounding)
+          setc(o[c], g, ip ? -x3 : __builtin_fmaf(x3, -2.0f, comp(b1[e], c)));  // (oracle: one rounding)
         }
-        lut[buf * LB + 4 * v + c] = o;
+      }
+      if constexpr (COL) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) lut[buf * LB + (4 * e + c) * 256 + tid] = o[c];
+      } else {
+        lut_store4<SCAN_LUT_ROTATE != 0, float4, G>(&lut[buf * LB + 4 * (e * 256 + tid)], o, tid & 63);
       }
     }
   };

@@ -6,13 +6,17 @@
 #   onepass   -DSCAN_LEAN_SPLIT=0   (one-pass k_scan_lean, profiles/scan_split_lut.md)
 #   nofill    -DPLAN_FILL_LEAD=0    (work items of one kind only, profiles/plan_fill_lead.md)
 #   noitembound -DSCAN_ITEM_BOUND=0 (tau_q from the per-wave k-th keys only, profiles/scan_item_bound.md)
+#   lutlinear -DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=0 (k_scan_lean's table build by row vectors, stores in the order
+#             c = 0..3: the scan before profiles/lut_store_banks.md)
+#   lutrotate -DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=1 (row vectors, stores rotated by the lane; same note)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/chameleon-rag-acceleration_amd/csrc
 L=$R/chameleon-rag-acceleration_amd/lib
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I$R/include -I$C"
 [ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0" "nofill:-DPLAN_FILL_LEAD=0" \
-  "noitembound:-DSCAN_ITEM_BOUND=0"
+  "noitembound:-DSCAN_ITEM_BOUND=0" \
+  "lutlinear:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=0" "lutrotate:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=1"
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   O=$R/chameleon-rag-acceleration_amd/lib/var/$name

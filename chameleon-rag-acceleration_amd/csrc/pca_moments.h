@@ -34,6 +34,10 @@ struct PcaPlan {
 PcaPlan pca_plan(int64_t n, int d, int64_t set_rows);
 // [mean_chunks][d] fp64 column sums, then [chunks][tiles][64 * 64] fp32 partial tiles
 size_t pca_workspace_bytes(const PcaPlan& p, int d);
+// The mean alone (the first half of launch_pca_moments, for a caller that centres its rows):
+// psum: pca_mean_chunks(n) * d doubles of workspace
+int pca_mean_chunks(int64_t n);
+void launch_pca_mean(const float* x, int64_t n, int d, double* psum, float* mean, hipStream_t s);
 // x [n][d]; mean [d]; scatter [d][d] (full, exactly symmetric, not divided by n); ws: pca_workspace_bytes
 void launch_pca_moments(const float* x, int64_t n, int d, const PcaPlan& p, void* ws, float* mean, float* scatter,
                         hipStream_t s);

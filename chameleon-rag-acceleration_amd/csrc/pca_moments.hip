@@ -193,6 +193,10 @@ __global__ __launch_bounds__(256) void k_pca_reduce(const float* __restrict__ pa
 
 }  // namespace
 
+int pca_mean_chunks(int64_t n) {
+  return (int)std::min<int64_t>((std::max<int64_t>(n, 1) + kPcaMeanRows - 1) / kPcaMeanRows, INT32_MAX);
+}
+
 PcaPlan pca_plan(int64_t n, int d, int64_t set_rows) {
   PcaPlan p;
   p.tb = (d + T - 1) / T;
@@ -207,7 +211,7 @@ PcaPlan pca_plan(int64_t n, int d, int64_t set_rows) {
   rows = (rows + KR - 1) / KR * KR;
   p.chunk_rows = rows;
   p.chunks = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + rows - 1) / rows, (int64_t)kPcaMaxChunks + 1);
-  p.mean_chunks = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + kPcaMeanRows - 1) / kPcaMeanRows, INT32_MAX);
+  p.mean_chunks = pca_mean_chunks(n);
   return p;
 }
 
@@ -216,13 +220,18 @@ size_t pca_workspace_bytes(const PcaPlan& p, int d) {
   return sums + (size_t)p.chunks * p.tiles * (T * T) * sizeof(float);
 }
 
+void launch_pca_mean(const float* x, int64_t n, int d, double* psum, float* mean, hipStream_t s) {
+  const int mc = pca_mean_chunks(n);
+  hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)mc, (unsigned)((d + T - 1) / T)), dim3(256), 0, s, x, n, d, psum);
+  hipLaunchKernelGGL(k_pca_mean, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, psum, mc, n, d, mean);
+}
+
 void launch_pca_moments(const float* x, int64_t n, int d, const PcaPlan& p, void* ws, float* mean, float* scatter,
                         hipStream_t s) {
   double* psum = reinterpret_cast<double*>(ws);
   const size_t sums = ((size_t)p.mean_chunks * d * sizeof(double) + 15) / 16 * 16;
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + sums);
-  hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)p.mean_chunks, (unsigned)p.tb), dim3(256), 0, s, x, n, d, psum);
-  hipLaunchKernelGGL(k_pca_mean, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, psum, p.mean_chunks, n, d, mean);
+  launch_pca_mean(x, n, d, psum, mean, s);
   const bool vec = (d & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(mean) & 15) == 0;
   const dim3 grid((unsigned)((int64_t)p.tiles * p.chunks));

@@ -144,6 +144,16 @@ SIGNATURES = {
     "ivfpq_clus_get_stats": _rc(c_handle, _intp, _f64p, c_i64p),
     "ivfpq_clus_set_pass_rows": SET_I64,
     "ivfpq_clus_rand_perm_prefix": _rc(_i64, _i64, _u64, c_i64p),
+    # the resident OPQ trainer (OPQMatrix.train_device)
+    "ivfpq_opq_create": _create(4),
+    "ivfpq_opq_free": HANDLE,
+    "ivfpq_opq_set_rows": F32_ROWS,
+    "ivfpq_opq_set_rows_device": ADD_DEVICE,
+    "ivfpq_opq_set_codebook": F32_ARRAY,
+    "ivfpq_opq_get_codebook": F32_ARRAY,
+    "ivfpq_opq_iterate": _rc(c_handle, c_f32p, _int, c_i64p, c_f32p),
+    "ivfpq_opq_set_chunk_rows": _rc(_i64),
+    "ivfpq_opq_get_plan": _rc(_i64, _int, _int, _intp, c_i64p, _intp),
     # how the host cuts a batch into chunks (host arithmetic; faiss_amd.index.*_split)
     "ivfpq_ivf_get_plan": _rc(_int, _i64, _intp, _intp),
     "ivfpq_ivf_get_query_chunk": _rc(_i64, *[_int] * 7, c_i64p),

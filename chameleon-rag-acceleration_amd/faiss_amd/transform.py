@@ -15,9 +15,15 @@ back out of the index (``my_faiss_extract_scripts/extract_FPGA_required_data.py:
 * ``OPQMatrix.train`` restates Faiss 1.7.1 ``OPQMatrix::train`` (centre the
   training set, random orthonormal start, then ``niter`` rounds of: rotate, PQ
   k-means (``niter_pq_0`` then ``niter_pq`` iterations, hot-started), encode /
-  decode, orthogonal Procrustes by SVD).  It runs on the host in numpy/float64
-  like Faiss's LAPACK path; its random start and k-means seeding are not Faiss's
-  (Faiss is not importable here), so trained matrices are not Faiss's either.
+  decode, orthogonal Procrustes by SVD).  By default it runs on the host in
+  numpy/float64 like Faiss's LAPACK path; ``train_device`` (and ``train`` with
+  ``gpu = True``) runs the same alternation with the rows resident in HBM
+  (csrc/opq_train.hip, csrc/opq.cpp: rotation, PQ Lloyd iterations, encode and the
+  cross matrix x^T rec on the GPU) and only the d x d2 SVD on the host
+  in float64.  Both make the same generator draws, so they start from the same
+  matrix and the same initial codebooks.  The random start and the k-means seeding
+  are not Faiss's (Faiss is not importable here), and empty PQ centroids are not
+  split, so trained matrices are not Faiss's either.
 * ``PCAMatrix.train`` takes the mean and the centred scatter matrix of the training rows on
   the GPU (``ivfpq_pca_moments_device``, csrc/pca_moments.hip: fp64 column sums, the scatter
   on the fp32 matrix cores in a fixed order) and the d x d eigendecomposition on the host in
@@ -157,6 +163,7 @@ class OPQMatrix(LinearTransform):
         self.niter_pq_0 = 40
         self.max_train_points = 256 * 256
         self.seed = 1234
+        self.gpu = False  # True: train() uploads the kept rows and takes train_device's path
         if d2 % self.M:
             raise RuntimeError("OPQMatrix: d_out must be a multiple of M")
 
@@ -197,6 +204,15 @@ class OPQMatrix(LinearTransform):
             x = x[np.sort(rng.choice(x.shape[0], self.max_train_points, replace=False))]
         if x.shape[0] < 256:
             raise RuntimeError("OPQMatrix.train needs at least 256 training vectors")
+        if self.gpu:
+            import torch
+
+            from ._handle import _default_device
+
+            with warnings.catch_warnings():  # (a read-only array is only read: the tensor is copied to the device)
+                warnings.simplefilter("ignore", UserWarning)
+                xd = torch.from_numpy(x).to(f"cuda:{_default_device()}")
+            return self._train_resident(xd, rng, None)
         d, d2 = self.d_in, self.d_out
         xt = x.astype(np.float64)
         xt -= xt.mean(0, keepdims=True)
@@ -213,6 +229,78 @@ class OPQMatrix(LinearTransform):
             u, _, vt = np.linalg.svd(xt.T @ rec, full_matrices=False)  # [d][d2] = U S V^T
             A = (u @ vt).T  # Procrustes: the rotation closest to mapping xt onto rec
         self.set_matrix(A.astype(np.float32))
+
+    def train_device(self, x, stream=None):
+        """train with the vectors already in HBM (torch float32 CUDA tensor [n, d_in]): the host
+        train's alternation with the rows, the codes and the codebooks resident on the GPU; per
+        outer round only the [d_in][d_out] cross matrix comes to the host, for the SVD."""
+        import torch
+
+        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != self.d_in or x.dtype != torch.float32
+                or not x.is_cuda):
+            raise RuntimeError(f"train_device: x must be a float32 CUDA tensor [n, {self.d_in}]")
+        rng = np.random.default_rng(self.seed)
+        if x.shape[0] > self.max_train_points:
+            keep = np.sort(rng.choice(x.shape[0], self.max_train_points, replace=False))
+            x = x.index_select(0, torch.from_numpy(keep).to(x.device))
+        if x.shape[0] < 256:
+            raise RuntimeError("OPQMatrix.train needs at least 256 training vectors")
+        self._train_resident(x.contiguous(), rng, stream)
+
+    def _train_resident(self, x, rng, stream):
+        """x: the kept rows on the GPU; rng: the generator after the subsample draw.  ``timing``
+        receives the seconds spent in the device rounds and in the host SVDs."""
+        import time
+
+        import torch
+
+        n, d, d2, M = x.shape[0], self.d_in, self.d_out, self.M
+        if self.A is None:  # the host train's draws, in its order: QR start, then 256 rows per sub-quantizer
+            q, r = np.linalg.qr(rng.standard_normal((d, d)))
+            A = (q * np.sign(np.diag(r))[None, :]).T[:d2].copy()
+        else:
+            A = self.A.astype(np.float64)
+        init = np.ascontiguousarray(np.concatenate([rng.choice(n, 256, replace=False) for _ in range(M)]), np.int64)
+        L = _lib.load()
+        cur = torch.cuda.current_stream(x.device)
+        s = cur.cuda_stream if stream is None else int(stream)
+        if s != cur.cuda_stream:
+            cur.synchronize()  # x's producer is on the current stream
+        h = _lib.c_handle()
+        _lib.check(L.ivfpq_opq_create(d, d2, M, x.device.index, ctypes.byref(h)))
+        cross = np.empty((d, d2), np.float32)
+        t_dev = t_svd = 0.0
+        try:
+            _lib.check(L.ivfpq_opq_set_rows_device(h, n, x.data_ptr(), ctypes.c_void_p(s)))
+            for it in range(self.niter):
+                A32 = np.ascontiguousarray(A, np.float32)
+                t0 = time.perf_counter()
+                _lib.check(L.ivfpq_opq_iterate(
+                    h, A32.ctypes.data_as(_lib.c_f32p), int(self.niter_pq_0 if it == 0 else self.niter_pq),
+                    init.ctypes.data_as(_lib.c_i64p) if it == 0 else None, cross.ctypes.data_as(_lib.c_f32p)))
+                t1 = time.perf_counter()
+                u, _, vt = np.linalg.svd(cross.astype(np.float64), full_matrices=False)  # [d][d2] = U S V^T
+                A = (u @ vt).T  # Procrustes: the rotation closest to mapping xt onto rec
+                t_dev += t1 - t0
+                t_svd += time.perf_counter() - t1
+        finally:
+            L.ivfpq_opq_free(h)
+        self.timing = {"device_s": t_dev, "svd_s": t_svd}
+        self.set_matrix(A.astype(np.float32))
+
+
+def opq_plan(n, d, d2):
+    """How the cross matrix of n rows, d -> d2 dimensions is split under the current chunk length
+    (ivfpq_opq_get_plan; host arithmetic): dict of chunks, chunk_rows, tiles."""
+    chunks, tiles, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _lib.check(_lib.load().ivfpq_opq_get_plan(int(n), int(d), int(d2), ctypes.byref(chunks), ctypes.byref(rows),
+                                              ctypes.byref(tiles)))
+    return {"chunks": chunks.value, "chunk_rows": rows.value, "tiles": tiles.value}
+
+
+def opq_set_chunk_rows(rows):
+    """The cross matrix's row chunk (test hook ivfpq_opq_set_chunk_rows); 0 restores the default."""
+    _lib.check(_lib.load().ivfpq_opq_set_chunk_rows(int(rows)))
 
 
 def pca_moments_device(x, stream=None):

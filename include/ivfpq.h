@@ -604,6 +604,42 @@ int ivfpq_clus_set_pass_rows(ivfpq_clus* h, int64_t rows);
 int ivfpq_clus_rand_perm_prefix(int64_t n, int64_t k, uint64_t seed, int64_t* out);
 
 /* ------------------------------------------------------------------------------------------
+ * The resident OPQ trainer (faiss.OPQMatrix::train: bench_gpu_1bn.py:480-495 "OPQ16,...", beir
+ * faiss_search.py OPQMatrix(768, 96, 384)).  A handle keeps the centred training rows, their
+ * rotation, the PQ codes and the [M][256][d2 / M] codebook in HBM; one ivfpq_opq_iterate is one
+ * outer round up to the Procrustes cross matrix, whose d x d2 SVD the caller takes on the host.
+ * The assignment is the first argmin in Faiss's fvec_L2sqr order (ivfpq_pq_add's codes bit for
+ * bit); the update adds every centroid's rows in ascending row order into one fp64 chain per
+ * (centroid, dimension), empty centroids keep their position (no splitting); the cross runs on
+ * the fp32 matrix cores per (64 x 64 tile, row chunk) with the chunks' partial tiles added in
+ * chunk order.  No floating-point atomics: two runs give the same bits.  create rejects
+ * d2 > d, d2 % M != 0 and M < 1 before any device call.  Same conventions, errors and locking
+ * as above.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ivfpq_opq ivfpq_opq;
+
+int ivfpq_opq_create(int d, int d2, int M, int device, ivfpq_opq** out);
+int ivfpq_opq_free(ivfpq_opq* h); /* free(NULL) returns 0 */
+/* The training rows x [n][d] (host): uploaded, their mean (fp64 column sums, rounded to fp32
+ * once) subtracted in fp32, and kept.  n M < 2^31 - 1. */
+int ivfpq_opq_set_rows(ivfpq_opq* h, int64_t n, const float* x);
+/* The same with x in HBM, read on `stream`; returns once the centred copy is in place. */
+int ivfpq_opq_set_rows_device(ivfpq_opq* h, int64_t n, const float* x, void* stream);
+int ivfpq_opq_set_codebook(ivfpq_opq* h, const float* cb); /* [M][256][d2 / M], host */
+int ivfpq_opq_get_codebook(ivfpq_opq* h, float* cb);
+/* One outer round with the rotation A [d2][d] (host): xp = xt A^T; when init_rows
+ * (int64 [M * 256], host) is not NULL centroid (m, j) is set to sub-vector m of row
+ * init_rows[m * 256 + j] of xp; niter_pq (>= 0) Lloyd iterations of every sub-quantizer; encode;
+ * cross [d][d2] (host) = sum_r xt_r (x) codebook[code_r].  Returns when cross is in place. */
+int ivfpq_opq_iterate(ivfpq_opq* h, const float* A, int niter_pq, const int64_t* init_rows, float* cross);
+/* The row chunk of the cross (process-wide; rounded up to 32 rows): rows > 0 sets it, 0
+ * (default) restores the length chosen from (n, d, d2) alone, as ivfpq_pca_set_chunk_rows. */
+int ivfpq_opq_set_chunk_rows(int64_t rows);
+/* How the cross splits n rows under that setting: chunks of chunk_rows rows, tiles =
+ * ceil(d / 64) * ceil(d2 / 64) output tiles.  Host arithmetic only.  Outputs are nullable. */
+int ivfpq_opq_get_plan(int64_t n, int d, int d2, int* chunks, int64_t* chunk_rows, int* tiles);
+
+/* ------------------------------------------------------------------------------------------
  * How the host cuts a batch into chunks ("Host-side splits").  Each getter returns
  * what the loop it names computes, from the same function: host arithmetic only, no handle, no
  * device call, outputs nullable.  The test suite uses them to assert that a batch is cut.

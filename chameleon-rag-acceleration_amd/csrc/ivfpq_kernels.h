@@ -109,7 +109,8 @@ struct ListPlan {
   int cap;           // bucket slots per list (>= queries in the batch)
   int32_t* recs;     // [max_items][16] work items: list, count, size, beg(2), pairs[4], dis0[4], 0 lead / 1 rest
   // [16]: n_items, n_items that are lead items (written by k_plan_items, or by the fused
-  // scan's first workgroup), the list scan's work counter, 0...
+  // scan's workgroup 0), the list scan's work counter (claims after each workgroup's first,
+  // which is its own index: item = grid + counter; zero between batches), 0...
   int32_t* hdr;
   int max_items;
   // [nq][nprobe][4 waves][k] per-wave sorted partial top-k, one 16-B record per entry:

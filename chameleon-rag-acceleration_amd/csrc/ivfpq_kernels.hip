@@ -1987,6 +1987,23 @@ struct Item {
 // final k-th; a stale read is only a looser bound).
 constexpr int QCAP = 256;  // per-wave candidate queue entries
 
+// THE FIRST CLAIM (SCAN_STATIC_CLAIM, profiles/scan_startup.md).  Every workgroup starts at the
+// same moment, so a first claim from the counter is gridDim.x returning atomics on one address
+// (they execute at the memory side, one after the other), a barrier behind them, and the first
+// record's loads only after both.  Which workgroup gets which of the first gridDim.x items
+// changes nothing in the result, so:
+//   1 (shipped): workgroup b starts with item b (if there is one) without touching the counter,
+//      its record's loads go out right behind the plan prefix, and every later claim is
+//      gridDim.x + atomicAdd(hdr + 2, 1): the same items in the same largest-first order.
+//      hdr[0..1] are written by workgroup 0; the merge zeroes hdr[2] as before;
+//   0: every claim from the counter (the scans before).
+#ifndef SCAN_STATIC_CLAIM
+#define SCAN_STATIC_CLAIM 1
+#endif
+// the item of a later claim, from the counter's value (applied where the value is consumed,
+// so that nothing waits for the atomic where it is issued)
+__device__ __forceinline__ int claimed_item(int t) { return SCAN_STATIC_CLAIM ? (int)gridDim.x + t : t; }
+
 
 // x / d for 0 <= x <= 2^24 by a float reciprocal (|error| <= 2 there) and a
 // correction from the remainder (an integer division is a ~40-instruction
@@ -2181,6 +2198,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
   const int nloc = a.list_hi - a.list_lo;
   const uint64_t lanemask_lt = (1ull << lane) - 1;
   const float inv_np = 1.0f / (float)a.nprobe;
+  DIAG_ONLY(const uint64_t d_entry = __builtin_amdgcn_s_memtime();)
   int n_items, n_items0 = 0;
   if (pl.fused) {
     const int2 t = fused_plan_prefix(pl, nloc, G, s_ex[0], s_ex[1], s_ord, reinterpret_cast<int*>(qi));
@@ -2240,6 +2258,18 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
     for (int g = 0; g < G; g++) it.q[g] = div_small((g < it.cnt ? it.pair[g] : it.pair[0]), a.nprobe, inv_np);
   };
 
+  int it_no = 0;
+  (void)it_no;
+  DIAG(12, d_entry);                       // (prologue stamps, in item 0's row: the kernel's entry,
+  DIAG(13, __builtin_amdgcn_s_memtime());  //  the plan prefix is done)
+#if SCAN_STATIC_CLAIM
+  // the item counts k_plan_items would have left (read by tests and tools)
+  if (pl.fused && blockIdx.x == 0 && tid == 0) {
+    pl.hdr[0] = n_items;
+    pl.hdr[1] = n_items0;
+  }
+  int cur = (int)blockIdx.x < n_items ? (int)blockIdx.x : -1;
+#else
   if (tid == 0) {
     const int t = atomicAdd(pl.hdr + 2, 1);
     s_next = t < n_items ? t : -1;
@@ -2250,9 +2280,10 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
   }
   __syncthreads();
   int cur = s_next;
+#endif
+  DIAG(14, __builtin_amdgcn_s_memtime());  // the first claim is known
   if (cur >= 0) unpack(fetch_rec(cur));
-  int it_no = 0;
-  (void)it_no;
+  DIAG(15, __builtin_amdgcn_s_memtime());  // the first record is unpacked
   // The next item's first loads -- its queries' running k-th keys (a stale
   // value is only a looser bound) and the first group of LUT rows -- are
   // issued at the end of the previous item's scan, before its partial writes,
@@ -2334,7 +2365,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_lists(ScanArgs a, ListPlan pl) 
         }
       }
     }
-    if (tid == 0) s_next = tnext < n_items ? tnext : -1;
+    if (tid == 0) s_next = claimed_item(tnext) < n_items ? claimed_item(tnext) : -1;
     if (tid < G) s_wb[tid] = f2ord(kInf);
     __syncthreads();  // (B) the LUT, s_next and s_wb are visible
     DIAG(1, __builtin_amdgcn_s_memtime());
@@ -2800,8 +2831,8 @@ __device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v) {  // lane i <- lan
 // LUT quarters alternate between two 16 KB buffers, pass p + 1's rows are loaded ahead
 // of pass p's gathers, and there is one barrier per pass (FOUR below).
 // REGISTER BUDGET, without scratch in every form:
-//   NP = 2 (shipped): 150 VGPRs of the 168 of three waves per SIMD, 40,000 B of LDS;
-//   NP = 4: 116 VGPRs of the 128 of four waves per SIMD, 40,000 B (of the 40,960 of four per CU).
+//   NP = 2 (shipped): 154 VGPRs of the 168 of three waves per SIMD, 40,000 B of LDS;
+//   NP = 4: 120 VGPRs of the 128 of four waves per SIMD, 40,000 B (of the 40,960 of four per CU).
 // They get there only through opq() below and through readfirstlane on the item's query
 // indices in unpack() (uniform, but computed on the VALU: it.q[] and its copies qix[]
 // otherwise take eight VGPRs across the scan; the two-pass form sat at exactly 168 before).
@@ -2894,6 +2925,7 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
   const int nloc = a.list_hi - a.list_lo;
   const float inv_np = 1.0f / (float)a.nprobe;
   const int rg = lane >> 4, re = lane & 15;  // row-packed top-k: lane 16 g + e = entry e of pair g
+  DIAG_ONLY(const uint64_t d_entry = __builtin_amdgcn_s_memtime();)
   const int2 nn = fused_plan_prefix(pl, nloc, G, s_ex[0], s_ex[1], s_ord, s_ws);
   const int n_items0 = nn.x, n_items = SPLIT ? __builtin_amdgcn_readfirstlane(nn.x + nn.y) : nn.x + nn.y;
   // SPLIT, opq(tid) / opq(lane): per-thread addresses and masks of the item loop are
@@ -2939,6 +2971,18 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
     return fused_record(a, pl, nloc, idx, n_items0, s_ex[0], s_ex[1], s_ord, G, opq(lane));
   };
 
+  int it_no = 0;  // (DIAG stamps)
+  (void)it_no;
+  DIAG(12, d_entry);                       // (prologue stamps, in item 0's row: the kernel's entry,
+  DIAG(13, __builtin_amdgcn_s_memtime());  //  the plan prefix is done)
+#if SCAN_STATIC_CLAIM
+  // the first record's loads go out right here, behind the prefix's last barrier
+  if (blockIdx.x == 0 && tid == 0) {  // the item counts k_plan_items would have left (read by tests and tools)
+    pl.hdr[0] = n_items;
+    pl.hdr[1] = n_items0;
+  }
+  int cur = (int)blockIdx.x < n_items ? (int)blockIdx.x : -1;
+#else
   if (tid == 0) {
     const int t = atomicAdd(pl.hdr + 2, 1);
     s_next = t < n_items ? t : -1;
@@ -2949,7 +2993,10 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
   }
   __syncthreads();
   int cur = s_next;
+#endif
+  DIAG(14, __builtin_amdgcn_s_memtime());  // the first claim is known
   if (cur >= 0) unpack(fetch_rec(cur));
+  DIAG(15, __builtin_amdgcn_s_memtime());  // the first record is unpacked
   CodeWords<M> cw[FOUR ? 1 : JB];
   uint32_t cq[FOUR ? JB : 1];  // (FOUR) the current pass's word of every chunk's code
   // An item's table rows: T1[l] (IP: a T3 row, ignored) and its G pairs' T3 rows,
@@ -3028,8 +3075,6 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
     }
   };
   if (kPre && cur >= 0) prefetch_t3(it.q);
-  int it_no = 0;  // (DIAG stamps)
-  (void)it_no;
 #if SCAN_ITEM_BOUND
   // the item whose rows are in s_rk: its pair count (0: none yet) and the query of its
   // pair `wave`, in SGPRs
@@ -3080,7 +3125,7 @@ __global__ __launch_bounds__(256, NP >= 4 ? 4 : NP == 2 ? 3 : 2) void k_scan_lea
     item_bound();  // the previous item's, in the shadow of the loads above
 #endif
     store_rows(0);
-    if (tid == 0) s_next = tnext < n_items ? tnext : -1;
+    if (tid == 0) s_next = claimed_item(tnext) < n_items ? claimed_item(tnext) : -1;
     if (const int t = opq(tid); t < G) s_wb[t] = f2ord(kInf);
     __syncthreads();  // (B) the LUT, s_next and s_wb are visible
     DIAG(1, __builtin_amdgcn_s_memtime());

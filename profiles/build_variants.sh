@@ -9,6 +9,8 @@
 #   lutlinear -DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=0 (k_scan_lean's table build by row vectors, stores in the order
 #             c = 0..3: the scan before profiles/lut_store_banks.md)
 #   lutrotate -DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=1 (row vectors, stores rotated by the lane; same note)
+#   dynclaim  -DSCAN_STATIC_CLAIM=0 (every work item claimed from the counter, a workgroup's first included:
+#             the scans before profiles/scan_startup.md)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/chameleon-rag-acceleration_amd/csrc
@@ -16,7 +18,8 @@ L=$R/chameleon-rag-acceleration_amd/lib
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I$R/include -I$C"
 [ $# -gt 0 ] || set -- "fourpass:-DSCAN_LEAN_PASSES=4" "onepass:-DSCAN_LEAN_SPLIT=0" "nofill:-DPLAN_FILL_LEAD=0" \
   "noitembound:-DSCAN_ITEM_BOUND=0" \
-  "lutlinear:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=0" "lutrotate:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=1"
+  "lutlinear:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=0" "lutrotate:-DSCAN_LUT_DWORD=0 -DSCAN_LUT_ROTATE=1" \
+  "dynclaim:-DSCAN_STATIC_CLAIM=0"
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   O=$R/chameleon-rag-acceleration_amd/lib/var/$name

@@ -3,7 +3,8 @@
 Slots per (workgroup, iteration), thread 0: 0 item start (barrier A), 1 LUT
 built (barrier B), 2 scan done, 3 partial writes done, 4 codes, 5 pairs |
 (0 lead / 1 rest item) << 8, 6 wave 0's cycles in the super-batch gathers, 7 its admitted
-candidates | drains << 32.
+candidates | drains << 32.  Item 0's row of a workgroup also holds the start-up stamps: 12 kernel
+entry, 13 plan prefix done, 14 first claim known, 15 first record unpacked.
 
 Usage (on the GPU box):
   bash profiles/build_variants.sh diag:"-DDIAG_STAMPS"     # here, before gpurun
@@ -47,14 +48,21 @@ def main():
     fn = L.ivfpq_diag_stamps
     fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
     buf = np.zeros(WG * ITEMS * SLOTS, np.uint64)
-    for _ in range(5):
+    # one batch at a time (the serial grid), then one batch with the grid of batches in flight
+    for inflight in (False, True):
+        ix.inflight = inflight
+        for _ in range(5):
+            ix.search_device(xd, 10)
+        torch.cuda.synchronize()
+        fn(buf.ctypes.data, buf.nbytes)  # clears
         ix.search_device(xd, 10)
-    torch.cuda.synchronize()
-    fn(buf.ctypes.data, buf.nbytes)  # clears
-    ix.search_device(xd, 10)
-    torch.cuda.synchronize()
-    assert fn(buf.ctypes.data, buf.nbytes) == 0
-    a = buf.reshape(WG, ITEMS, SLOTS).astype(np.int64)
+        torch.cuda.synchronize()
+        assert fn(buf.ctypes.data, buf.nbytes) == 0
+        print(f"==== inflight {int(inflight)}")
+        report(buf.reshape(WG, ITEMS, SLOTS).astype(np.int64))
+
+
+def report(a):
     valid = a[:, :, 0] > 0
     t0, t1, t2, t3, n, ck, push, tau = [a[:, :, i] for i in range(8)]
     kind = (ck >> 8) & 1
@@ -90,6 +98,18 @@ def main():
     k0_end = np.where(valid & (kind == 0), t3, 0).max()
     k1 = valid & (kind == 1)
     early = k1 & (t0 < k0_end)
+    # the start-up of every workgroup that scanned something (stamps 12..15 of its first item's row)
+    e, pf, cl, up = (a[:, 0, i][act] for i in (12, 13, 14, 15))
+    b0, b1 = t0[:, 0][act], t1[:, 0][act]
+    if (e > 0).all():
+        for name, v in (("entry -> prefix done", pf - e), ("prefix -> first claim known", cl - pf),
+                        ("claim -> first record unpacked", up - cl), ("unpacked -> barrier A", b0 - up),
+                        ("barrier A -> first LUT built", b1 - b0), ("entry -> first LUT built", b1 - e)):
+            print(f"start-up ({act.sum()} workgroups) {name:32s} mean {v.mean():8.0f} p50 {np.median(v):8.0f} "
+                  f"p90 {np.percentile(v, 90):8.0f} max {v.max():8.0f}")
+        # (per workgroup: the counters of different XCDs have different origins)
+        sp = last[act] - e
+        print(f"WG span from the kernel's entry mean {sp.mean():.0f} max {sp.max():.0f} cycles")
     print(f"rest items started before the last lead item ended: {early.sum()} of {k1.sum()}; "
           f"their scan mean {(t2 - t1)[early].mean() if early.any() else 0:.0f} vs later "
           f"{(t2 - t1)[k1 & ~early].mean() if (k1 & ~early).any() else 0:.0f}")

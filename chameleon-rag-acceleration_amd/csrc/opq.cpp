@@ -42,6 +42,7 @@ struct ivfpq_opq : StreamOrder {
   int device = 0, d = 0, d2 = 0, M = 0;
   int64_t n = 0;  // rows held (0: none yet)
   bool have_cb = false;
+  bool have_codes = false;  // d_codes holds the final assignment of an iterate over the rows held
   hipStream_t stream = nullptr;
   std::mutex mu;
   DevBuf d_raw, d_psum, d_mean, d_xt, d_xp, d_codes, d_labels, d_zero, d_cb, d_sum, d_cnt, d_obj, d_pass, d_AT, d_idx,
@@ -66,6 +67,7 @@ struct ivfpq_opq : StreamOrder {
     require(n_ * M < (int64_t)INT32_MAX, "OPQ: n M must stay below 2^31 - 1");
     (void)checked_opq_plan(n_, d, d2);
     const size_t nm = (size_t)n_ * M;
+    have_codes = false;
     d_psum.ensure(sizeof(double) * (size_t)pca_mean_chunks(n_) * d);
     d_mean.ensure(sizeof(float) * (size_t)d);
     d_xt.ensure(sizeof(float) * (size_t)n_ * d);
@@ -137,6 +139,7 @@ struct ivfpq_opq : StreamOrder {
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(cross, d_cross.p, sizeof(float) * (size_t)d * d2, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
+    have_codes = true;
   }
 };
 
@@ -190,6 +193,15 @@ int ivfpq_opq_get_codebook(ivfpq_opq* h, float* cb) {
     require(h->have_cb, "OPQ: no codebook yet");
     const size_t bytes = sizeof(float) * (size_t)h->ncent() * h->dsub();
     HIPCHECK(hipMemcpyAsync(cb, h->d_cb.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  });
+}
+
+int ivfpq_opq_get_codes(ivfpq_opq* h, uint8_t* codes) {
+  return with_handle(h, [&] {
+    require(codes != nullptr, "null output pointer");
+    require(h->have_codes, "OPQ: no codes yet (ivfpq_opq_iterate first)");
+    HIPCHECK(hipMemcpyAsync(codes, h->d_codes.p, (size_t)h->n * h->M, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
   });
 }

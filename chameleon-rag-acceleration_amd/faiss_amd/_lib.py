@@ -152,6 +152,7 @@ SIGNATURES = {
     "ivfpq_opq_set_codebook": F32_ARRAY,
     "ivfpq_opq_get_codebook": F32_ARRAY,
     "ivfpq_opq_iterate": _rc(c_handle, c_f32p, _int, c_i64p, c_f32p),
+    "ivfpq_opq_get_codes": _rc(c_handle, c_u8p),
     "ivfpq_opq_set_chunk_rows": _rc(_i64),
     "ivfpq_opq_get_plan": _rc(_i64, _int, _int, _intp, c_i64p, _intp),
     # how the host cuts a batch into chunks (host arithmetic; faiss_amd.index.*_split)

@@ -632,6 +632,10 @@ int ivfpq_opq_get_codebook(ivfpq_opq* h, float* cb);
  * init_rows[m * 256 + j] of xp; niter_pq (>= 0) Lloyd iterations of every sub-quantizer; encode;
  * cross [d][d2] (host) = sum_r xt_r (x) codebook[code_r].  Returns when cross is in place. */
 int ivfpq_opq_iterate(ivfpq_opq* h, const float* A, int niter_pq, const int64_t* init_rows, float* cross);
+/* Test hook, as ivfpq_opq_set_chunk_rows: codes [n][M] (host) of the last ivfpq_opq_iterate's final
+ * assignment, the one its cross was built from.  An error before the first iterate over the
+ * rows held (ivfpq_opq_set_rows starts over).  OPQMatrix does not use it. */
+int ivfpq_opq_get_codes(ivfpq_opq* h, uint8_t* codes);
 /* The row chunk of the cross (process-wide; rounded up to 32 rows): rows > 0 sets it, 0
  * (default) restores the length chosen from (n, d, d2) alone, as ivfpq_pca_set_chunk_rows. */
 int ivfpq_opq_set_chunk_rows(int64_t rows);

@@ -8,7 +8,8 @@ comparisons are ``assert_array_equal``.  Shapes (n, d, d2, M, chunk_rows):
 (37, 24, 16, 4, default) one partial K step; (300, 72, 40, 20, 64) dsub = 2, two row tiles,
 five chunks, the last of 44 rows; (257, 130, 96, 8, 128) dsub = 12, sub-quantizer 5 across the
 64-column tile edge, a last chunk of one row; (37, 10, 10, 2, default) dsub = 5, which has no
-LDS assignment kernel and takes launch_pq_encode_flat.
+LDS assignment kernel and takes launch_pq_encode_flat.  Real values, every other width, centring
+and a handle used more than once are tests/test_gpu_opq_assign.py and tests/test_gpu_opq_rounds.py.
 """
 import ctypes
 import functools
@@ -144,6 +145,45 @@ def test_training_repeats_and_entry_points_agree():
     _, A = trained("train_device")
     np.testing.assert_array_equal(trained.__wrapped__("train_device")[1], A)
     np.testing.assert_array_equal(trained("train")[1], A)
+
+
+# DESIGN.md 4j, "Tests": the PQ MSE (pq_mse of the centred rows under the trained rotation) of the host
+# float64 trainer on correlated(4096, 32, 2), niter 6, niter_pq_0 8, niter_pq 2, at five seeds.  The
+# seed-to-seed spread is the noise floor of the alternation; the device trainer at the first of these
+# seeds must lie inside the host's range widened by its own width on each side.
+HOST_SEEDS = (1234, 1, 2, 3, 4)
+HOST_MSE = (243.41114847518844, 184.83728016427463, 246.85872539239386, 286.3353613916478, 206.79266249503348)
+MSE_LO = min(HOST_MSE) - (max(HOST_MSE) - min(HOST_MSE))  # 83.339
+MSE_HI = max(HOST_MSE) + (max(HOST_MSE) - min(HOST_MSE))  # 387.833
+
+
+def rotated_mse(x, A):
+    xc = x - x.mean(0)
+    return pq_mse((xc.astype(np.float64) @ A.T.astype(np.float64)).astype(np.float32), 4)
+
+
+@functools.lru_cache(maxsize=None)
+def host_mse():
+    """The five host trainings (CPU, float64), once per session."""
+    x, out = correlated(4096, 32, 2), []
+    for seed in HOST_SEEDS:
+        opq = OPQMatrix(32, 4)
+        opq.niter, opq.niter_pq_0, opq.niter_pq, opq.seed = 6, 8, 2, seed
+        assert opq.gpu is False
+        opq.train(x)
+        out.append(rotated_mse(x, opq.A))
+    return tuple(out)
+
+
+def test_device_trainer_against_the_host_trainer():
+    x, A = trained("train_device")  # opq.seed is HOST_SEEDS[0], the default
+    assert OPQMatrix(32, 4).seed == HOST_SEEDS[0]
+    dev, host = rotated_mse(x, A), host_mse()
+    print(f"PQ MSE device {dev!r} host {host!r} interval [{MSE_LO:.3f}, {MSE_HI:.3f}]")
+    assert MSE_LO <= dev <= MSE_HI
+    lo, hi = min(host), max(host)  # the same rule from this session's host trainings
+    assert 2 * lo - hi <= dev <= 2 * hi - lo
+    assert all(MSE_LO <= v <= MSE_HI for v in host)  # the recorded interval still describes the host trainer
 
 
 def test_training_reduced_output_dimension():

@@ -1,10 +1,15 @@
-// Flat fp32 rows (IndexFlat) behind the C-ABI of include/ivfpq.h.
+// Flat fp32 rows (IndexFlat), or half rows (GpuIndexFlat* with useFloat16), behind the C-ABI of
+// include/ivfpq.h.
 // faiss.IndexFlat / IndexFlatL2 / IndexFlatIP: the raw vectors, every row compared with
 // every query (flat_scan.hip).  The rows live in a CodeStore of 4 d bytes per row; their
 // |y|^2 (launch_row_norms' tree order) are computed once, when the rows are added, and kept
 // beside the image.  Every k runs the fused scan: no distance is written to memory.
+// A handle made by ivfpq_flat_index_create_f16 keeps 2 d bytes per row: rows are rounded to
+// half as they are added, with the norms of the rounded rows, the queries of a search chunk
+// are rounded into a workspace, and the scan is flat_scan_f16.hip's; everything else is shared.
 #include "code_store.h"
 #include "flat_scan.h"
+#include "flat_scan_f16.h"
 #include "ivf_flat.h"  // launch_fill_empty
 #include "ivfpq.h"
 #include "ivfpq_test.h"
@@ -13,16 +18,19 @@ using namespace chivf;
 
 struct ivfpq_flat_index : CodeStore {
   int d = 0, metric = IVFPQ_METRIC_L2;
+  bool f16 = false;            // the image holds halves (ivfpq_flat_index_create_f16)
   DevBuf d_norms;              // [cap] |y|^2 of the image's rows
   int64_t norms_cap = 0;
   int64_t rows_from_host = 0;  // rows copied from the host since create (ivfpq_flat_index_get_stats)
   int64_t reallocs = 0;        // times the image was reallocated
   int64_t range_rows = 0;      // > 0: the row range of a scan workgroup (ivfpq_flat_index_set_range_rows)
+  DevBuf w_xh;                 // [chunk][d] the rounded queries of a half image's search chunk
   DevBuf w_xn, w_D, w_I, p_tau, p_partD, p_partI, p_tmpD, p_tmpI;
 
   ivfpq_flat_index() : CodeStore("IndexFlat") {}
   bool ip() const { return metric == IVFPQ_METRIC_INNER_PRODUCT; }
   float* base() const { return d_codes.as<float>(); }
+  _Float16* base_h() const { return d_codes.as<_Float16>(); }
 
   // room for n more rows in the image and the norms beside it
   void reserve_rows(int64_t n, hipStream_t s) {
@@ -37,6 +45,12 @@ struct ivfpq_flat_index : CodeStore {
   // n rows (device-resident, or host rows when from_host) behind the image with their norms;
   // returns when they are in place
   void add_rows(int64_t n, const float* x, bool from_host, hipStream_t s) {
+    if (f16) {  // host rows pass through the fp32 staging buffer, chunk by chunk
+      if (from_host) add_host(n, x, sizeof(float) * (size_t)d, [&](int64_t c) { add_half(c, w_x.as<float>(), stream); });
+      else add_half(n, x, s);
+      if (from_host) rows_from_host += n;
+      return;
+    }
     reserve_rows(n, s);
     if (from_host) quiesce();
     else order_after(s);
@@ -47,6 +61,31 @@ struct ivfpq_flat_index : CodeStore {
     HIPCHECK(hipStreamSynchronize(s));
     ntotal += n;
     if (from_host) rows_from_host += n;
+  }
+
+  // n device-resident fp32 rows rounded to half behind the image, with the norms of the
+  // rounded rows; returns when they are in place
+  void add_half(int64_t n, const float* xd, hipStream_t s) {
+    reserve_rows(n, s);
+    order_after(s);
+    launch_rows_to_half(xd, n, d, base_h() + (size_t)ntotal * d, d_norms.as<float>() + ntotal, nullptr, s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    ntotal += n;
+  }
+
+  // rows [i0, i0 + n) of a half image to the host, widened to fp32 through the staging buffer
+  void read_rows_widened(int64_t i0, int64_t n, float* out) {
+    quiesce();
+    const int64_t rows = host_rows(n, sizeof(float) * (size_t)d);
+    w_x.ensure(sizeof(float) * (size_t)rows * d);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t c = std::min(rows, n - r0);
+      launch_half_to_float(base_h() + (size_t)(i0 + r0) * d, c * d, w_x.as<float>(), stream);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipMemcpyAsync(out + (size_t)r0 * d, w_x.p, sizeof(float) * (size_t)c * d, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+    }
   }
 
   void reset_rows() {
@@ -74,9 +113,33 @@ struct ivfpq_flat_index : CodeStore {
     const size_t tmp_lists = (size_t)std::max(1, pl.S / pl.fan);
     p_tmpD.ensure(sizeof(float) * tmp_lists * qc * k);
     p_tmpI.ensure(sizeof(int64_t) * tmp_lists * qc * k);
+    if (f16) w_xh.ensure(sizeof(_Float16) * (size_t)qc * d);
     for (int64_t q0 = 0; q0 < n; q0 += qc) {
       const int64_t c = std::min(qc, n - q0);
       const float* xq = xd + q0 * d;
+      if (f16) {  // the chunk's queries rounded once, their norms and cleared bounds in the same pass
+        launch_rows_to_half(xq, c, d, w_xh.as<_Float16>(), w_xn.as<float>(), p_tau.as<uint32_t>(), s);
+        FlatScanHArgs a;
+        a.x = w_xh.as<_Float16>();
+        a.xn = w_xn.as<float>();
+        a.nq = c;
+        a.d = d;
+        a.base = base_h();
+        a.bn = d_norms.as<float>();
+        a.nb = ntotal;
+        a.k = k;
+        a.ip = ip();
+        a.tau = p_tau.as<uint32_t>();
+        a.partD = p_partD.as<float>();
+        a.partI = p_partI.as<int64_t>();
+        a.tmpD = p_tmpD.as<float>();
+        a.tmpI = p_tmpI.as<int64_t>();
+        a.D = D + q0 * k;
+        a.I = I + q0 * k;
+        launch_flat_search_h(a, pl, s);
+        HIPCHECK(hipGetLastError());
+        continue;
+      }
       launch_row_norms(xq, c, d, w_xn.as<float>(), s);
       FlatScanArgs a;
       a.x = xq;
@@ -118,7 +181,7 @@ struct ivfpq_flat_index : CodeStore {
 
 extern "C" {
 
-int ivfpq_flat_index_create(int device, int d, int metric, ivfpq_flat_index** out) {
+static int create_flat(int device, int d, int metric, bool f16, ivfpq_flat_index** out) {
   return guarded([&] {
     require(out != nullptr, "null output pointer");
     require(d >= 1, "IndexFlat: d must be at least 1 (d = " + std::to_string(d) + ")");
@@ -126,9 +189,18 @@ int ivfpq_flat_index_create(int device, int d, int metric, ivfpq_flat_index** ou
     auto h = std::make_unique<ivfpq_flat_index>();
     h->d = d;
     h->metric = metric;
-    h->row_bytes = sizeof(float) * (size_t)d;
+    h->f16 = f16;
+    h->row_bytes = (f16 ? sizeof(_Float16) : sizeof(float)) * (size_t)d;
     open_store(std::move(h), device, out);
   });
+}
+
+int ivfpq_flat_index_create(int device, int d, int metric, ivfpq_flat_index** out) {
+  return create_flat(device, d, metric, false, out);
+}
+
+int ivfpq_flat_index_create_f16(int device, int d, int metric, ivfpq_flat_index** out) {
+  return create_flat(device, d, metric, true, out);
 }
 
 int ivfpq_flat_index_free(ivfpq_flat_index* h) { return free_handle(h); }
@@ -190,7 +262,8 @@ int ivfpq_flat_index_get_rows(ivfpq_flat_index* h, int64_t i0, int64_t n, float*
     require(i0 >= 0 && n >= 0 && i0 + n <= h->ntotal, "row range outside [0, ntotal)");
     if (n == 0) return;
     require(out != nullptr, "null output pointer");
-    h->read_rows(i0, n, reinterpret_cast<uint8_t*>(out), h->row_bytes);
+    if (h->f16) h->read_rows_widened(i0, n, out);
+    else h->read_rows(i0, n, reinterpret_cast<uint8_t*>(out), h->row_bytes);
   });
 }
 

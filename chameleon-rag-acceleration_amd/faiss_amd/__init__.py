@@ -54,3 +54,14 @@ from . import contrib  # noqa: F401
 from .contrib import ivf_tools  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """faiss.StandardGpuResources, GpuIndexFlatConfig, GpuIndexFlat, GpuIndexFlatL2, GpuIndexFlatIP: defined in
+    ``faiss_amd.gpu``, which is loaded at the first use of one of them.  (``dir(faiss_amd)`` lists the names
+    imported above; these five are resolved here.)"""
+    if name in ("StandardGpuResources", "GpuIndexFlatConfig", "GpuIndexFlat", "GpuIndexFlatL2", "GpuIndexFlatIP"):
+        from importlib import import_module
+
+        return getattr(import_module(__name__ + ".gpu"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -131,7 +131,8 @@ SIGNATURES = {
         get_plan=_rc(_int, _i64, _i64, _int, _intp, _intp, _intp, c_i64p, c_i64p)),
     # flat fp32 rows (IndexFlat / IndexFlatL2 / IndexFlatIP)
     **_family(
-        "ivfpq_flat_index_", create=_create(3), get_dims=_dims(2), add=F32_ROWS, add_device=ADD_DEVICE,
+        "ivfpq_flat_index_", create=_create(3), create_f16=_create(3), get_dims=_dims(2), add=F32_ROWS,
+        add_device=ADD_DEVICE,
         get_rows=_rc(c_handle, _i64, _i64, c_f32p), get_stats=_rc(c_handle, c_i64p, c_i64p, c_i64p),
         set_range_rows=SET_I64,
         get_plan=_rc(_i64, _i64, _int, _i64, _intp, c_i64p, _intp, _intp, _intp, _intp, c_i64p)),

@@ -529,6 +529,16 @@ int ivfpq_bin_get_plan(int d, int64_t ntotal, int64_t nq, int k, int* stride, in
 typedef struct ivfpq_flat_index ivfpq_flat_index;
 
 int ivfpq_flat_index_create(int device, int d, int metric, ivfpq_flat_index** out);
+/* faiss.GpuIndexFlat(res, d, metric, config) with config.useFloat16 = true: the same handle
+ * over an image of IEEE halves, 2 d bytes per row.  add / add_device still take fp32 rows and
+ * round them to half (nearest even; a value beyond the half range becomes +-inf, as in
+ * Faiss-GPU, and is not trapped) with the squared norm of the rounded row; get_rows returns
+ * the stored halves widened to fp32; a search rounds its fp32 queries the same way and runs
+ * csrc/flat_scan_f16.hip: half inputs, fp32 products and sums on v_mfma_f32_16x16x32_f16,
+ * L2 = max(0, |x|^2 + |y|^2 - 2 <x, y>) with the norms of the rounded values.  Ties, padding,
+ * ranges and every other entry point are those of ivfpq_flat_index_create's handle; the
+ * summation order inside a product is the matrix instruction's, not the oracle's chain. */
+int ivfpq_flat_index_create_f16(int device, int d, int metric, ivfpq_flat_index** out);
 int ivfpq_flat_index_free(ivfpq_flat_index* h); /* free(NULL) returns 0 */
 /* Index.reset(): drop the rows. */
 int ivfpq_flat_index_reset(ivfpq_flat_index* h);

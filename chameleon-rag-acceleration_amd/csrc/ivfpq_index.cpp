@@ -106,6 +106,7 @@ struct ivfpq_index {
   int slot = 0;  // the workspace of the current (last begun) device call
   uint64_t uses = 0;
   bool inflight = inflight_default();
+  bool f16lut = false;  // ivfpq_set_float16_lut: the scans' LUT entries in half (ScanArgs::f16lut)
   int fault_inj = 0;  // test hook (ivfpq_set_fault_injection): ListPlan::fault
   std::vector<uint64_t> tau_seed;  // test hook (ivfpq_debug_seed_tau): the next batch's starting bounds
   std::mutex mu;
@@ -161,7 +162,7 @@ struct ivfpq_index {
   ListPlan make_plan(int64_t nq, int np, int k, hipStream_t s, bool leave_free = false) {
     const int nloc = std::max(list_hi - list_lo, 1);
     Work& w = W();
-    const int G = list_scan_group(M, k);
+    const int G = list_scan_group(M, k, f16lut);
     ListPlan pl;
     pl.cap = (int)nq;
     pl.max_items = list_scan_max_items(nq * np, nloc, G);
@@ -231,8 +232,9 @@ struct ivfpq_index {
     // DESIGN.md section 4); one batch at a time, and in the shard flow's preassigned
     // searches, where the sweep was inconclusive, it takes them all
     // (and the four-pass scan is capped at scan_inflight_wgs_per_cu() workgroups per CU)
-    pl.grid = scan_lists_grid(M, k, pl.fused != 0, leave_free ? scan_inflight_free_cus(M, k, pl.fused != 0) : 0,
-                              leave_free ? scan_inflight_wgs_per_cu(M, k, pl.fused != 0) : 0, &pl.lds_pad);
+    pl.grid = scan_lists_grid(M, k, pl.fused != 0, leave_free ? scan_inflight_free_cus(M, k, pl.fused != 0, f16lut) : 0,
+                              leave_free ? scan_inflight_wgs_per_cu(M, k, pl.fused != 0, f16lut) : 0, &pl.lds_pad,
+                              f16lut);
     return pl;
   }
 
@@ -537,7 +539,7 @@ struct ivfpq_index {
       W().w_lists.ensure(sizeof(int64_t) * qc * np);
       W().w_dis0.ensure(sizeof(float) * qc * np);
     }
-    const int G = list_scan_group(M, k);
+    const int G = list_scan_group(M, k, f16lut);
     // tables computed ahead (tables_dev): exactly the entry of the token, which
     // this search consumes
     int pi = -1;
@@ -567,7 +569,7 @@ struct ivfpq_index {
       } else {
         planned =
             coarse_launch(xq, c, np, W().w_dis0.as<float>(), W().w_lists.as<int64_t>(), s, &plan, W().w_T3.as<float>(),
-                          nullptr, 0, /*hoist: the scan is not k_scan_lean*/ !(k <= 16 && M <= 16));
+                          nullptr, 0, /*hoist: the scan is not k_scan_lean*/ f16lut || !(k <= 16 && M <= 16));
         lists = W().w_lists.as<int64_t>();
         if (!planned)
           launch_plan_count(lists, ip() ? nullptr : W().w_dis0.as<float>(), xq, cq.d_cent.as<float>(), c, d, np,
@@ -598,6 +600,7 @@ struct ivfpq_index {
       a.ip = ip() ? 1 : 0;
       a.list_lo = list_lo;
       a.list_hi = list_hi;
+      a.f16lut = f16lut ? 1 : 0;
       a.outD = D + q0 * k;
       a.outI = I + q0 * k;
       const int ts = mark_begin(ST_SCAN, s);
@@ -951,6 +954,7 @@ int ivfpq_set_list_range(ivfpq_index* h, int lo, int hi) {
   return with_handle(h, [&] {
     require(0 <= lo && lo <= hi && hi <= h->nlist, "invalid list range");
     require(h->ntotal == 0 && h->q.n == 0, "set the list range before adding vectors");
+    require(!h->f16lut || (lo == 0 && hi == h->nlist), "a list-range shard has no float16 lookup tables");
     h->list_lo = lo;
     h->list_hi = hi;
     h->dirty = true;  // the device image (list order) follows the range
@@ -1015,6 +1019,16 @@ int ivfpq_set_inflight(ivfpq_index* h, int on) {
 }
 
 int ivfpq_get_inflight(const ivfpq_index* h) { return h ? (h->inflight ? 1 : 0) : -1; }
+
+int ivfpq_set_float16_lut(ivfpq_index* h, int on) {
+  return with_handle(h, [&] {
+    require(!on || (h->list_lo == 0 && h->list_hi == h->nlist), "a list-range shard has no float16 lookup tables");
+    h->quiesce();  // the workspaces' plans are sized by the pairs per item of the scan in use
+    h->f16lut = on != 0;
+  });
+}
+
+int ivfpq_get_float16_lut(const ivfpq_index* h) { return h ? (h->f16lut ? 1 : 0) : -1; }
 
 int ivfpq_overlap_built(void) { return 1; }
 

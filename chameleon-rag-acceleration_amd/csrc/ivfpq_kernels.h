@@ -156,6 +156,7 @@ struct ScanArgs {
   int M;
   int ip;                // 1: inner product (LUT = -T3, output similarity = -key)
   int list_lo, list_hi;  // only lists in [list_lo, list_hi) are scanned (shard range)
+  int f16lut = 0;        // 1: LUT entries clamped and rounded to half (k_scan_lists_h; repair_probe follows)
   float* outD;           // [nq][k]
   int64_t* outI;         // [nq][k]
 };
@@ -175,15 +176,18 @@ void launch_plan_items(const ListPlan& pl, const int64_t* list_off, int lo, int 
 // whether the list scan can plan its own items (nloc lists, at most max_items items, code size M)
 bool scan_fused_plan(int nloc, int max_items, int M);
 
-int list_scan_group(int M, int k);  // pairs per work item (G) used for (M, k)
+// pairs per work item (G) used for (M, k); f16lut: of the half-LUT scan (ScanArgs::f16lut),
+// here and in the three sizing functions below
+int list_scan_group(int M, int k, bool f16lut = false);
 int list_scan_max_items(int64_t npairs, int nloc, int G);
 // persistent grid on all but free_cus CUs: the workgroups per CU resident of the kernel
 // that launch_scan_lists picks for (M, k, fused = ListPlan::fused)
 // wgs_cap (> 0, the four-pass k_scan_lean only): at most that many workgroups per CU;
 // *lds_pad (nullable: no cap) receives the dynamic LDS the launch must ask for (ListPlan::lds_pad)
-int scan_lists_grid(int M, int k, bool fused, int free_cus = 0, int wgs_cap = 0, int* lds_pad = nullptr);
-int scan_inflight_free_cus(int M, int k, bool fused);    // free_cus of a search with batches in flight
-int scan_inflight_wgs_per_cu(int M, int k, bool fused);  // wgs_cap of a search with batches in flight
+int scan_lists_grid(int M, int k, bool fused, int free_cus = 0, int wgs_cap = 0, int* lds_pad = nullptr,
+                    bool f16lut = false);
+int scan_inflight_free_cus(int M, int k, bool fused, bool f16lut = false);    // free_cus of a search with batches in flight
+int scan_inflight_wgs_per_cu(int M, int k, bool fused, bool f16lut = false);  // wgs_cap of a search with batches in flight
 bool scan_supported_M(int M);
 // list scan + probe merge; ev_lists (nullable): two events recorded around the list-scan kernel alone
 void launch_scan_lists(const ScanArgs& a, const ListPlan& plan, hipStream_t s, hipEvent_t* ev_lists = nullptr);

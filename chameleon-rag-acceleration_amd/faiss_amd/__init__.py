@@ -57,10 +57,12 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """faiss.StandardGpuResources, GpuIndexFlatConfig, GpuIndexFlat, GpuIndexFlatL2, GpuIndexFlatIP: defined in
-    ``faiss_amd.gpu``, which is loaded at the first use of one of them.  (``dir(faiss_amd)`` lists the names
-    imported above; these five are resolved here.)"""
-    if name in ("StandardGpuResources", "GpuIndexFlatConfig", "GpuIndexFlat", "GpuIndexFlatL2", "GpuIndexFlatIP"):
+    """faiss.StandardGpuResources, GpuIndexFlatConfig, GpuIndexFlat, GpuIndexFlatL2, GpuIndexFlatIP,
+    GpuClonerOptions, GpuIndexIVFPQ, GpuIndexIVFFlat, index_cpu_to_gpu: defined in ``faiss_amd.gpu``, which is
+    loaded at the first use of one of them.  (``dir(faiss_amd)`` lists the names imported above; these are
+    resolved here.)"""
+    if name in ("StandardGpuResources", "GpuIndexFlatConfig", "GpuIndexFlat", "GpuIndexFlatL2", "GpuIndexFlatIP",
+                "GpuClonerOptions", "GpuIndexIVFPQ", "GpuIndexIVFFlat", "index_cpu_to_gpu"):
         from importlib import import_module
 
         return getattr(import_module(__name__ + ".gpu"), name)

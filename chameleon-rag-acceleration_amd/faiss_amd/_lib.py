@@ -103,7 +103,7 @@ SIGNATURES = {
         coarse_device=_rc(c_handle, _i64, _vp, _vp, _vp, _vp),
         coarse_tables_device=_rc(c_handle, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _u64p),
         serve_request=_rc(c_handle, c_u8p, _i64, _int, _int, _int, _int, c_u8p, _i64, c_i64p),
-        set_inflight=SET_INT, get_inflight=HANDLE, set_timing=SET_INT, get_timing=_rc(c_handle, _f64p, c_i64p),
+        set_inflight=SET_INT, get_inflight=HANDLE, set_float16_lut=SET_INT, get_float16_lut=HANDLE, set_timing=SET_INT, get_timing=_rc(c_handle, _f64p, c_i64p),
         get_error_count=I64_ARRAY, get_repair_stats=_rc(c_handle, c_i64p, c_i64p),
         get_repair_log=_rc(c_handle, ctypes.POINTER(ctypes.c_uint32), _int, _intp), set_fault_injection=SET_INT,
         debug_workspace=_rc(c_handle, _int, _int, _vp, _i64, c_i64p), debug_seed_tau=_rc(c_handle, _i64, _vp)),

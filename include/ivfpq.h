@@ -147,6 +147,14 @@ int ivfpq_search_preassigned_tables_device(ivfpq_index* h, int64_t n, const floa
  * blocks streamed through one GPU index, bench_gpu_1bn.py:788-806. */
 int ivfpq_set_inflight(ivfpq_index* h, int on);
 int ivfpq_get_inflight(const ivfpq_index* h);
+/* Float16 lookup tables (faiss GpuClonerOptions::useFloat16 on an IVF-PQ index,
+ * bench_gpu_sift1m.py:73-79): with on = 1 every later search of the handle -- host, device,
+ * preassigned, with precomputed tables, with batches in flight -- scans with LUT entries
+ * clamped to +-65504 and rounded once to IEEE half (nearest even); sums stay fp32 in m order.
+ * Per handle, default 0, may be changed between searches (waits for those in flight); not
+ * written to index files.  A list-range shard (ivfpq_set_list_range) rejects it. */
+int ivfpq_set_float16_lut(ivfpq_index* h, int on);
+int ivfpq_get_float16_lut(const ivfpq_index* h);
 /* 1: the overlap is available (kept for callers of the r04 interface). */
 int ivfpq_overlap_built(void);
 

@@ -178,8 +178,15 @@ struct ivfpq_index {
       HIPCHECK(hipMemsetAsync(w.p_hdr.p, 0, w.p_hdr.bytes, s));
     }
     pl.ks = part_stride(k);
-    w.p_part.ensure(sizeof(uint4) * nq * np * 4 * pl.ks);
-    w.p_N.ensure(sizeof(uint2) * nq * np * 4);
+    // New memory may hold another handle's tagged records, and a young workspace repeats that handle's
+    // epochs: a lost store would then read them as its own (part_tag names the epoch and the slot, not
+    // the handle).  Cleared once per allocation, so a foreign record carries tag 0.
+    for (auto [b, need] : {std::pair<DevBuf*, size_t>{&w.p_part, sizeof(uint4) * nq * np * 4 * pl.ks},
+                           std::pair<DevBuf*, size_t>{&w.p_N, sizeof(uint2) * nq * np * 4}}) {
+      if (b->p && b->bytes >= need) continue;
+      b->ensure(need);
+      HIPCHECK(hipMemsetAsync(b->p, 0, b->bytes, s));
+    }
     w.p_pd0.ensure(sizeof(float) * nq * np);
     if (!w.p_evlog.p) {
       w.p_evlog.ensure(sizeof(uint32_t) * 8 * kEvLog);

@@ -1,6 +1,7 @@
 """Index contents whose rows reach a scan in a chosen key order (NumPy and the tests' own
-references only), for tests/test_gpu_scan_order.py, tests/test_gpu_exact_scan_order.py and
-their preconditions in tests/test_scan_order_cpu.py.
+references only), for tests/test_gpu_scan_order.py, tests/test_gpu_ivfpq_f16lut_order.py (the
+float16-LUT scan: pq_contents(half=True)), tests/test_gpu_exact_scan_order.py and their
+preconditions in tests/test_scan_order_cpu.py.
 
 Every scan of the library prunes on a running bound, so which of its branches run depends on
 the order in which the keys arrive.  For one *designated query* the builders here return
@@ -113,8 +114,17 @@ def pq_keys(cent_l, cb, q, codes, metric):
     return -(y @ q) if metric == IP else ((q - y) ** 2).sum(1)
 
 
-def pq_contents(shape, metric, order, nlist=4, place=(0, 1, 2, 3), sizes=SIZES):
-    """An IVF-PQ index of `nlist` lists of which place[j] holds sizes[j] rows in `order`."""
+def pq_contents(shape, metric, order, nlist=4, place=(0, 1, 2, 3), sizes=SIZES, half=False):
+    """An IVF-PQ index of `nlist` lists of which place[j] holds sizes[j] rows in `order`.
+
+    half=True: the order is that of the float16-LUT key (tests/ivfpq_f16lut_ref.py pair_keys), which c.keys
+    then holds.  The draws are the same; for L2 about 290 entries of sub-quantizers 0 and 1 (up to about
+    68 000) are inexact in half, odd ones in [2048, 4096) are exact ties, and with q[0] = -3 and the
+    centroids' coordinate 0 made non-negative the largest of every list clamp at 65504.
+    For the inner product 256 j is exact in half, so the half and fp32 tables would coincide: sub-quantizer
+    1's entry j is (257 j, 0, ...) instead, inexact for 228 j, with j = 255 (65535) clamped."""
+    if half:
+        import ivfpq_f16lut_ref as RH
     d, M = PQ_SHAPES[shape]
     dsub = d // M
     rng = np.random.default_rng(seed_of("pq", shape, metric, order, nlist))
@@ -122,16 +132,21 @@ def pq_contents(shape, metric, order, nlist=4, place=(0, 1, 2, 3), sizes=SIZES):
     cb = rng.integers(-2, 3, size=(M, 256, dsub)).astype(F)
     cb[:2] = 0
     cb[0, :, 0] = np.arange(256)
-    cb[1, :, 0] = np.arange(256) * (256 if metric == IP else 1)
+    cb[1, :, 0] = np.arange(256) * ((257 if half else 256) if metric == IP else 1)
     q = rng.integers(-3, 4, size=d).astype(F)
     if metric == IP:
         q[0] = q[dsub] = 1
+    elif half:  # sub-quantizer 0's entry j is j^2 + 2 j (cent - q): at least 255^2 + 1530 > 65504 in every list
+        q[0], cent[:, 0] = -3, np.abs(cent[:, 0])
     c = SimpleNamespace(d=d, M=M, metric=metric, order=order, nlist=nlist, place=tuple(place), sizes=tuple(sizes),
-                        cent=cent, cb=cb, q=q, xq=queries(rng, q), keys=[], list_ids=[])
+                        cent=cent, cb=cb, q=q, xq=queries(rng, q), keys=[], list_ids=[], half=half)
     list_no, codes, ids = [], [], []
     for j, n in enumerate(sizes):
         cand = rng.integers(0, 256, size=(DRAW * n, M), dtype=np.uint8)
-        k64 = pq_keys(cent[place[j]], cb, q, cand, metric)
+        if half:
+            k64 = RH.pair_keys(q, cent[place[j]], cb, cand, ip=metric == IP).astype(np.float64)
+        else:
+            k64 = pq_keys(cent[place[j]], cb, q, cand, metric)
         pos = arrange(k64.astype(F), n, order, rng)
         c.keys.append(k64[pos])
         c.list_ids.append(list_ids(j, n))
@@ -152,6 +167,15 @@ def dis0(c, xq, rows):
     d2 = ((xq[:, None, :].astype(np.float64) - cc) ** 2).sum(-1)
     assert d2.max() < 2 ** 24
     return np.where(rows >= 0, d2, 0).astype(F)
+
+
+def pq_lists(c):
+    """(list_codes, list_ids) per list number of the contents c, as tests/ivfpq_f16lut_ref.py takes them."""
+    codes = [np.zeros((0, c.M), np.uint8)] * c.nlist
+    ids = [np.zeros(0, np.int64)] * c.nlist
+    for j, l in enumerate(c.place):
+        codes[l], ids[l] = c.codes[c.list_no == l], c.list_ids[j]
+    return codes, ids
 
 
 def probe_rows(c, nq, which):

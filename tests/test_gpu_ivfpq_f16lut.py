@@ -96,6 +96,33 @@ def test_lost_partial_lists_are_repaired_with_half_entries():
 
 
 @pytest.mark.gpu
+def test_lost_partial_lists_of_a_first_batch_are_not_read_from_a_freed_handle():
+    """A new handle's first batch has the epoch, and so the tags, of every earlier handle's first batch.  The
+    workspace of an inner-product handle of the same shape is freed just before, so that the allocator may hand
+    the same block to the L2 handle: its lost slots must not be taken from the records left there (negated
+    similarities, far below every L2 key), which the workspace clears when it allocates."""
+    import gc
+
+    c_ip, c = case(64, True), case(64)
+    for _ in range(3):
+        old = gpu_index(c_ip, 64, True)
+        old.search(c_ip["xq"], 10)
+        del old
+        gc.collect()
+        ix = gpu_index(c, 64)
+        before = ix.repair_stats()[1]
+        ix.set_fault_injection(3)
+        try:
+            got = ix.search(c["xq"], 10)
+        finally:
+            ix.set_fault_injection(0)
+        check(got, c, 10)
+        assert ix.repair_stats()[1] > before
+        del ix
+        gc.collect()
+
+
+@pytest.mark.gpu
 def test_batches_in_flight():
     import torch
 

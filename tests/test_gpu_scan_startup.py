@@ -94,9 +94,9 @@ def make_pair(M, metric, nlist=NLIST, lo=0, hi=None, big=None):
     return ix, ox, cent
 
 
-def build_rows(n_items, lists, all_lead=False):
+def build_rows(n_items, lists, all_lead=False, g=G):
     """Probe rows over `lists` (every one non-empty) that make exactly n_items work items
-    at G = 4, and the number of lead items among them."""
+    at g pairs per item, and the number of lead items among them."""
     if n_items == 0:
         return np.full((1, 1), -1, np.int64), 0
     if all_lead or n_items < 12:
@@ -108,7 +108,7 @@ def build_rows(n_items, lists, all_lead=False):
     assert len(t) <= len(lists)
     rows = [[lists[j]] for j in range(len(t))]
     for j, tj in enumerate(t):
-        c1 = G * (tj - 1)
+        c1 = g * (tj - 1)
         assert c1 < len(rows)
         for s in range(c1):  # a later probe of the c1 rows behind its own
             rows[(j + 1 + s) % len(rows)].append(lists[j])
@@ -118,7 +118,7 @@ def build_rows(n_items, lists, all_lead=False):
     return out, len(t)
 
 
-def expected_items(rows):
+def expected_items(rows, g=G):
     """(items, lead items) of the rows by the planner's rule, every probed list usable."""
     c = {}
     for row in rows:
@@ -127,7 +127,7 @@ def expected_items(rows):
             if l >= 0:
                 c.setdefault(int(l), [0, 0])[0 if first else 1] += 1
                 first = False
-    return (sum(-(-(c0 + c1) // G) for c0, c1 in c.values()), sum(-(-c0 // G) for c0, _ in c.values()))
+    return (sum(-(-(c0 + c1) // g) for c0, c1 in c.values()), sum(-(-c0 // g) for c0, _ in c.values()))
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,5 @@
-"""The preconditions of the key-order GPU tests (tests/test_gpu_scan_order.py and
-tests/test_gpu_exact_scan_order.py), held on the CPU with NumPy, the oracle and the tests' own
+"""The preconditions of the key-order GPU tests (tests/test_gpu_scan_order.py, its float16-LUT
+sibling tests/test_gpu_ivfpq_f16lut_order.py and tests/test_gpu_exact_scan_order.py), held on the CPU with NumPy, the oracle and the tests' own
 references: for every (shape, metric, order) those tests use, the designated query's keys are
 pairwise distinct in fp32 (and exact integers below 2^24 wherever the data is integer-valued),
 the rows sorted by label have the promised order, every list has the size the GPU tests were
@@ -13,6 +13,7 @@ import pytest
 import indexflat_ref as RFLAT
 import indexsq_ref as RSQ
 import ivfflat_ref as RIVF
+import ivfpq_f16lut_ref as RH
 import ivfsq_ref as RIVFSQ
 import scan_order as SO
 from oracle import oracle as O
@@ -101,6 +102,63 @@ def test_ivfpq_contents(shape, nlist, place, metric, order):
         for k in (K, 1000):
             D, I = ox.search_preassigned(c.xq[:1], k, rows, SO.dis0(c, c.xq[:1], rows))
             assert_topk(I[0], D[0], c, l, k, metric)
+
+
+# ---------------------------------------------------------------- IVF-PQ, float16 lookup tables
+PQ_GRID_H = [(s, 4, (0, 1, 2, 3)) for s in SO.PQ_SHAPES] + \
+            [(s, 1032, (0, 1023, 1024, 1031)) for s in ("d32_m8", "d64_m32")]
+
+
+def half_ties(lut):
+    """Which fp32 entries lie exactly half-way between two neighbouring halves (inside the finite range)."""
+    x = lut.astype(np.float64)
+    h = RH.entries(lut).astype(np.float16)
+    with np.errstate(over="ignore"):  # the neighbour above 65504
+        other = np.where(h.astype(np.float64) < x, np.nextafter(h, np.float16(np.inf)), np.nextafter(h, np.float16(-np.inf)))
+    return (np.abs(x) < 65504) & (h.astype(np.float64) != x) & \
+        (np.abs(x - h.astype(np.float64)) == np.abs(x - other.astype(np.float64)))
+
+
+@ORDERS
+@METRICS
+@pytest.mark.parametrize("shape,nlist,place", PQ_GRID_H, ids=[f"{s}_nlist{n}" for s, n, _ in PQ_GRID_H])
+def test_ivfpq_half_contents(shape, nlist, place, metric, order):
+    """pq_contents(half=True), what tests/test_gpu_ivfpq_f16lut_order.py searches: the rows are in `order`
+    by the float16-LUT key, the half reference finds the expected ids, the half and fp32 tables give
+    different results for the batch, and the designated query's tables hold exact ties and clamped entries."""
+    ip = metric == SO.IP
+    c = SO.pq_contents(shape, metric, order, nlist, place, half=True)
+    assert c.sizes == (4700, 1537, 300, 0) and c.xq.shape == (13, c.d)
+    assert (c.xq[:5] == c.q).all() and not (c.xq[5:] == c.q).all(1).any()
+    np.testing.assert_array_equal(np.bincount(c.list_no, minlength=nlist)[list(place)], c.sizes)
+    for l, n in enumerate(c.sizes):
+        assert len(c.keys[l]) == n
+        assert_order(c.keys[l], c.list_ids[l], order, integer=True)  # pairwise distinct in fp32
+    lcodes, lids = SO.pq_lists(c)
+    for l in (0, 1, 2):
+        rows = SO.probe_rows(c, 1, [l])
+        for k in (K, 1000):
+            D, I = RH.search_preassigned(c.xq[:1], k, rows, SO.dis0(c, c.xq[:1], rows), c.cent, c.cb, lcodes, lids, ip)
+            assert_topk(I[0], D[0], c, l, k, metric)
+    # the batch the GPU test searches: a build that ran the fp32 scan under the flag would differ
+    rows = SO.probe_rows(c, len(c.xq), range(4))
+    dq = SO.dis0(c, c.xq, rows)
+    Dh, Ih = RH.search_preassigned(c.xq, 1000, rows, dq, c.cent, c.cb, lcodes, lids, ip)
+    Df, If = RH.search_preassigned(c.xq, 1000, rows, dq, c.cent, c.cb, lcodes, lids, ip, half=False)
+    assert not np.array_equal(Dh, Df) and not np.array_equal(Ih, If)
+    if place == (0, 1, 2, 3):  # the fp32-LUT reference is the oracle, so the difference is the entries' alone
+        ox = O.OracleIVFPQ(c.d, nlist, c.M, metric=SO.metric_id(metric))
+        ox.set_trained(c.cent, c.cb)
+        ox.add_preencoded(c.list_no, c.codes, c.ids)
+        Do, Io = ox.search_preassigned(c.xq, 1000, rows, dq)
+        np.testing.assert_array_equal(Io, If)
+        np.testing.assert_array_equal(Do, Df)
+    # the designated query's fp32 entries over the three lists: exact ties and entries beyond +-65504
+    T3q = O.ip_table(c.q[None], c.cb)[0]
+    T1 = O.precompute_T1(np.ascontiguousarray(c.cent[list(place[:3])]), c.cb)
+    lut = np.stack([RH.lut32(T3q, T1[j], ip) for j in range(3)])
+    assert half_ties(lut).any(axis=(1, 2)).all()
+    assert (np.abs(lut) > 65504).any(axis=(1, 2)).all()
 
 
 # ---------------------------------------------------------------- the exact scans

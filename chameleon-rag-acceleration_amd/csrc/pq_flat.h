@@ -32,6 +32,8 @@ struct PqScanPlan {
   int S = 0;
 };
 PqScanPlan pq_scan_plan(int M, int k, int64_t nq, int64_t nb);
+// the same split for a scan of G queries per workgroup (pq_scan_plan: G = 4; the 4-bit scan: pq_flat4.h)
+PqScanPlan pq_scan_plan_group(int G, int k, int64_t nq, int64_t nb);
 
 // tab [nq][M][256] (launch_ip_table / launch_l2_table), codes [nb][M], 1 <= nb < 2^31 - 1.
 // Writes partD / partI [S][nq][k]: per (range, wave) the k best of its rows as

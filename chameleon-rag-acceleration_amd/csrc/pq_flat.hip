@@ -27,58 +27,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fvec_tree.h"
 #include "pq_flat.h"
 #include "scan_topk.h"
 
 namespace chivf {
 
 namespace {
-
-// Faiss-1.7.1 AVX reduction order (or_tree in oracle/ivfpq_oracle.c; the same
-// function as tree<> in ivfpq_kernels.hip).
-template <int KIND, class FX, class FY>
-__device__ __forceinline__ float tree(FX fx, FY fy, int d) {
-  float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int i = 0;
-  for (; i + 8 <= d; i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float p;
-      if (KIND == K_IP) {
-        p = fx(i + j) * fy(i + j);
-      } else {
-        float t = fx(i + j) - fy(i + j);
-        p = t * t;
-      }
-      a8[j] = a8[j] + p;
-    }
-  }
-  float a4[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) a4[j] = a8[j + 4] + a8[j];
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++) {
-    // pass 0: the 4-wide remainder (d - i >= 4); pass 1: the masked tail
-    if (pass == 0 && i + 4 > d) continue;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (i + j < d) {
-        float p;
-        if (KIND == K_IP) {
-          p = fx(i + j) * fy(i + j);
-        } else {
-          float t = fx(i + j) - fy(i + j);
-          p = t * t;
-        }
-        a4[j] = a4[j] + p;
-      }
-    }
-    if (pass == 0) i += 4;
-  }
-  float h0 = a4[0] + a4[1];
-  float h1 = a4[2] + a4[3];
-  return h0 + h1;
-}
 
 // ------------------------------------------------------------------ L2 table
 // k_ip_tiles' tiling: a workgroup takes (16 queries, sub-quantizer m), thread t holds
@@ -300,9 +255,12 @@ void launch_pq_encode_flat(const float* x, int64_t n, int d, const float* cb, in
 // partial lists than the merge takes cheaply (S * k <= 12288 entries per query).
 PqScanPlan pq_scan_plan(int M, int k, int64_t nq, int64_t nb) {
   (void)M;
+  return pq_scan_plan_group(kScanGroup, k, nq, nb);
+}
+
+PqScanPlan pq_scan_plan_group(int G, int k, int64_t nq, int64_t nb) {
   PqScanPlan p;
-  (void)k;
-  p.G = kScanGroup;
+  p.G = G;
   const int64_t groups = (nq + p.G - 1) / p.G;
   const int64_t tiles = std::max<int64_t>(1, (nb + kPqTileRows - 1) / kPqTileRows);
   int64_t ranges = (1024 + groups - 1) / std::max<int64_t>(groups, 1);

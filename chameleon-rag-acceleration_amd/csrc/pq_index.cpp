@@ -1,7 +1,8 @@
 // Flat PQ (IndexPQ) behind the C-ABI of include/ivfpq.h.
 // faiss.IndexPQ: no coarse quantizer and no inverted lists -- one product quantizer
 // over the raw vectors, every code scanned for every query (pq_flat.hip).  The codes
-// live in a CodeStore of M bytes per row.
+// live in a CodeStore of M * nbits / 8 bytes per row: nbits = 8 (pq_flat.hip) or 4
+// (pq_flat4.hip: 16 centroids per sub-quantizer, two sub-quantizers per byte).
 #include <cstring>
 #include <vector>
 
@@ -11,16 +12,20 @@
 #include "ivfpq_test.h"
 #include "kmeans.h"
 #include "pq_flat.h"
+#include "pq_flat4.h"
 
 using namespace chivf;
 
 namespace {
 
-// queries per chunk of a flat-PQ search: the tables (M KiB per query) within kChunkBytes,
-// the grid's y extent (shared by the handle and ivfpq_pq_debug_plan)
-int64_t pq_query_chunk(int M, int64_t n) {
-  return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / ((size_t)M * 1024)), 4096}));
+// queries per chunk of a flat-PQ search: the tables (M KiB per query at 8 bits, 64 M bytes
+// at 4) within kChunkBytes, the grid's y extent (shared by the handle and ivfpq_pq_debug_plan)
+int64_t pq_query_chunk(int M, int64_t n, int nbits = 8) {
+  const size_t table_bytes = (size_t)M * sizeof(float) << nbits;
+  return std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)(kChunkBytes / table_bytes), 4096}));
 }
+
+constexpr const char* kPq4ShapeText = "nbits=4 needs M to be a multiple of 32 (32 ... 256)";
 
 const char* pq_supported_M_text() { return " not supported on the GPU (8, 16, 32, 48, 64, 80, 96, 112, 128)"; }
 
@@ -29,7 +34,7 @@ const char* pq_supported_M_text() { return " not supported on the GPU (8, 16, 32
 struct ivfpq_pq_index : CodeStore {
   int d = 0, M = 0, nbits = 8, ksub = 256, metric = IVFPQ_METRIC_L2;
   bool trained = false;
-  std::vector<float> codebook;  // [M][256][d / M]
+  std::vector<float> codebook;  // [M][ksub][d / M]
   DevBuf d_cb;
   DevBuf w_tab, w_pD, w_pI, w_D, w_I;  // tables, partial lists, results of the host entry points
 
@@ -48,13 +53,16 @@ struct ivfpq_pq_index : CodeStore {
   void add_dev(int64_t n, const float* xd, hipStream_t s) {
     reserve(n, s);
     order_after(s);
-    launch_pq_encode_flat(xd, n, d, d_cb.as<float>(), M, row(ntotal), s);
+    if (nbits == 4)
+      launch_pq_encode4(xd, n, d, d_cb.as<float>(), M, row(ntotal), s);
+    else
+      launch_pq_encode_flat(xd, n, d, d_cb.as<float>(), M, row(ntotal), s);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     ntotal += n;
   }
 
-  int64_t query_chunk(int64_t n) const { return pq_query_chunk(M, n); }
+  int64_t query_chunk(int64_t n) const { return pq_query_chunk(M, n, nbits); }
 
   // c device-resident queries -> D, I (device), all on s
   void search_chunk(const float* xd, int64_t c, int k, float* D, int64_t* I, hipStream_t s) {
@@ -62,16 +70,23 @@ struct ivfpq_pq_index : CodeStore {
       launch_fill_empty(D, I, c * k, ip(), s);
       return;
     }
-    w_tab.ensure(sizeof(float) * c * M * 256);
+    const bool four = nbits == 4;
+    w_tab.ensure(sizeof(float) * c * M * ksub);
     if (ip())
       launch_ip_table(xd, c, d, d_cb.as<float>(), M, ksub, w_tab.as<float>(), s);
+    else if (four)
+      launch_l2_table4(xd, c, d, d_cb.as<float>(), M, w_tab.as<float>(), s);
     else
       launch_l2_table(xd, c, d, d_cb.as<float>(), M, w_tab.as<float>(), s);
-    const PqScanPlan pl = pq_scan_plan(M, k, c, ntotal);
+    const PqScanPlan pl = four ? pq_scan4_plan(k, c, ntotal) : pq_scan_plan(M, k, c, ntotal);
     w_pD.ensure(sizeof(float) * pl.S * c * k);
     w_pI.ensure(sizeof(int64_t) * pl.S * c * k);
-    launch_pq_scan(w_tab.as<float>(), c, d_codes.as<uint8_t>(), ntotal, M, k, ip(), pl, w_pD.as<float>(),
-                   w_pI.as<int64_t>(), s);
+    if (four)
+      launch_pq_scan4(w_tab.as<float>(), c, d_codes.as<uint8_t>(), ntotal, M, k, ip(), pl, w_pD.as<float>(),
+                      w_pI.as<int64_t>(), s);
+    else
+      launch_pq_scan(w_tab.as<float>(), c, d_codes.as<uint8_t>(), ntotal, M, k, ip(), pl, w_pD.as<float>(),
+                     w_pI.as<int64_t>(), s);
     launch_merge_topk(pl.S, c, k, w_pD.as<float>(), w_pI.as<int64_t>(), D, I, s, ip());
     HIPCHECK(hipGetLastError());
   }
@@ -109,17 +124,19 @@ int ivfpq_pq_create(int d, int M, int nbits, int metric, int device, ivfpq_pq_in
   return guarded([&] {
     require(out != nullptr, "null output pointer");
     require(d > 0 && M > 0, "d and M must be positive");
+    require(nbits == 8 || nbits == 4, "only nbits=8 and nbits=4 are supported");
+    require(nbits == 8 || pq_flat4_supported_M(M), kPq4ShapeText);
     require(d % M == 0, "d must be a multiple of M");
-    require(nbits == 8, "only nbits=8 is supported");
-    require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
+    require(nbits == 4 || pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
     require(d <= 2048, "d > 2048 not supported");
     require(metric == IVFPQ_METRIC_L2 || metric == IVFPQ_METRIC_INNER_PRODUCT, "unknown metric");
     auto h = std::make_unique<ivfpq_pq_index>();
     h->d = d;
     h->M = M;
     h->nbits = nbits;
+    h->ksub = 1 << nbits;
     h->metric = metric;
-    h->row_bytes = (size_t)M;
+    h->row_bytes = (size_t)M * nbits / 8;
     open_store(std::move(h), device, out);
   });
 }
@@ -129,15 +146,15 @@ int ivfpq_pq_free(ivfpq_pq_index* h) { return free_handle(h); }
 int ivfpq_pq_train(ivfpq_pq_index* h, int64_t n, const float* x, int niter, uint64_t seed) {
   return with_handle(h, [&] {
     require(x != nullptr && n > 0, "empty training set");
-    const int d = h->d, M = h->M, dsub = d / M;
+    const int d = h->d, M = h->M, dsub = d / M, ksub = h->ksub;
     // the k-means of ivfpq_train's sub-quantizers (assignment on the GPU, double-precision
     // mean on the host), on the handle's stream
     KMeans km(h->stream);
     std::vector<float> sub((size_t)n * dsub);
-    std::vector<float> cb((size_t)M * 256 * dsub);
+    std::vector<float> cb((size_t)M * ksub * dsub);
     for (int m = 0; m < M; m++) {
       for (int64_t i = 0; i < n; i++) std::memcpy(&sub[(size_t)i * dsub], x + i * d + m * dsub, sizeof(float) * dsub);
-      km.kmeans(sub.data(), n, dsub, 256, niter, seed + 1 + (uint64_t)m, cb.data() + (size_t)m * 256 * dsub);
+      km.kmeans(sub.data(), n, dsub, ksub, niter, seed + 1 + (uint64_t)m, cb.data() + (size_t)m * ksub * dsub);
     }
     HIPCHECK(hipStreamSynchronize(h->stream));
     h->codebook = std::move(cb);
@@ -148,7 +165,7 @@ int ivfpq_pq_train(ivfpq_pq_index* h, int64_t n, const float* x, int niter, uint
 int ivfpq_pq_set_trained(ivfpq_pq_index* h, const float* codebook) {
   return with_handle(h, [&] {
     require(codebook != nullptr, "null codebook");
-    h->codebook.assign(codebook, codebook + (size_t)h->M * 256 * (h->d / h->M));
+    h->codebook.assign(codebook, codebook + (size_t)h->M * h->ksub * (h->d / h->M));
     h->upload_codebook();
   });
 }
@@ -232,22 +249,33 @@ int ivfpq_pq_get_codes(ivfpq_pq_index* h, int64_t i0, int64_t n, uint8_t* out) {
   });
 }
 
-// Test hook (ivfpq_test.h): host arithmetic only, no handle and no device call.
-int ivfpq_pq_debug_plan(int M, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
-                        int64_t* query_chunk) {
+// How a search is split (ivfpq.h): host arithmetic only, no handle and no device call.
+int ivfpq_pq_get_plan(int M, int nbits, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
+                      int64_t* query_chunk) {
   return guarded([&] {
-    require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
+    require(nbits == 8 || nbits == 4, "only nbits=8 and nbits=4 are supported");
+    if (nbits == 4)
+      require(pq_flat4_supported_M(M), kPq4ShapeText);
+    else
+      require(pq_flat_supported_M(M), "M=" + std::to_string(M) + pq_supported_M_text());
     require(k >= 1 && k <= kMaxK, "k must be in [1, " + std::to_string(kMaxK) + "]");
     require(nq >= 1, "query count must be positive");
     require(nb >= 1 && nb < (int64_t)INT32_MAX, "IndexPQ holds at most 2^31 - 2 codes");
-    const int64_t qc = pq_query_chunk(M, nq);
-    const PqScanPlan pl = pq_scan_plan(M, k, std::min(nq, qc), nb);
+    const int64_t qc = pq_query_chunk(M, nq, nbits);
+    const int64_t c = std::min(nq, qc);
+    const PqScanPlan pl = nbits == 4 ? pq_scan4_plan(k, c, nb) : pq_scan_plan(M, k, c, nb);
     if (G) *G = pl.G;
     if (ranges) *ranges = pl.ranges;
     if (rows) *rows = pl.rows;
     if (S) *S = pl.S;
     if (query_chunk) *query_chunk = qc;
   });
+}
+
+// Test hook (ivfpq_test.h): the 8-bit plan.
+int ivfpq_pq_debug_plan(int M, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
+                        int64_t* query_chunk) {
+  return ivfpq_pq_get_plan(M, 8, k, nq, nb, G, ranges, rows, S, query_chunk);
 }
 
 }  // extern "C"

@@ -111,7 +111,8 @@ SIGNATURES = {
     **_family(
         "ivfpq_pq_", create=_create(5), get_dims=_dims(4), is_trained=HANDLE, train=TRAIN, set_trained=F32_ARRAY,
         add=F32_ROWS, add_device=ADD_DEVICE, add_codes=U8_ROWS, get_codebook=F32_ARRAY, get_codes=GET_CODES,
-        debug_plan=_rc(_int, _int, _i64, _i64, _intp, _intp, c_i64p, _intp, c_i64p)),
+        debug_plan=_rc(_int, _int, _i64, _i64, _intp, _intp, c_i64p, _intp, c_i64p),
+        get_plan=_rc(_int, _int, _int, _i64, _i64, _intp, _intp, c_i64p, _intp, c_i64p)),
     # IVF over raw vectors (IndexIVFFlat)
     **_family("ivfpq_ivfflat_", **_ivf(c_f32p), create=_create(4), get_dims=_dims(3), train=TRAIN,
               set_trained=F32_ARRAY),

@@ -236,15 +236,17 @@ def _parse_pq(r: "_Reader") -> dict:
     search_type = r.fmt("i")
     r.fmt("B")  # encode_signs
     r.fmt("i")  # polysemous_ht
-    if pd != d or nbits != 8 or M == 0 or d % M or (is_trained and cb.size != M * 256 * (d // M)):
-        raise RuntimeError("unsupported PQ shape (8-bit codes)")
+    ksub, code_size = 1 << min(nbits, 8), M * nbits // 8
+    if (pd != d or nbits not in (4, 8) or M == 0 or d % M or (M * nbits) % 8
+            or (is_trained and cb.size != M * ksub * (d // M))):
+        raise RuntimeError("unsupported PQ shape (8-bit or 4-bit codes)")
     if search_type != 0:
         raise RuntimeError("only IndexPQ search_type ST_PQ is supported")
-    if codes.size != ntotal * M:
+    if codes.size != ntotal * code_size:
         raise RuntimeError("IndexPQ codes do not match ntotal")
     return {"kind": "pq", "d": d, "ntotal": ntotal, "M": M, "nbits": nbits, "metric": metric,
-            "is_trained": is_trained, "codebook": cb.reshape(M, 256, d // M) if cb.size else cb,
-            "codes": codes.reshape(ntotal, M)}
+            "is_trained": is_trained, "codebook": cb.reshape(M, ksub, d // M) if cb.size else cb,
+            "codes": codes.reshape(ntotal, code_size)}
 
 
 def parse_pq(buf: bytes) -> dict:
@@ -259,7 +261,7 @@ def parse_pq(buf: bytes) -> dict:
 
 
 def serialize_pq(d, M, nbits, metric, codebook, codes, is_trained=True) -> bytes:
-    """The inverse of parse_pq: codes uint8 [ntotal][M]."""
+    """The inverse of parse_pq: codes uint8 [ntotal][M * nbits / 8]."""
     codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
     code_size = M * nbits // 8
     return b"".join([FOURCC_PQ, _header(d, codes.size // code_size, is_trained, metric),

@@ -679,7 +679,9 @@ class IndexIVFPQ(_IVFIndex):
 class IndexPQ(_HandleIndex):
     """faiss.IndexPQ: one product quantizer over the raw vectors, every code
     scanned for every query (beir faiss_search.py:168-224, nbits_experiments_fix_m.py:89).
-    Labels are positions: there is no id map, as in Faiss."""
+    Labels are positions: there is no id map, as in Faiss.  ``nbits`` is 8, or 4 with M a
+    multiple of 32 up to 256 (16 centroids per sub-quantizer, ``code_size = M / 2``:
+    sub-quantizer 2i in the low nibble of byte i, 2i + 1 in the high one)."""
 
     _c = _lib.Family("ivfpq_pq_")
     _faiss_name = "IndexPQ"
@@ -697,14 +699,14 @@ class IndexPQ(_HandleIndex):
 
     @property
     def code_size(self):
-        return self.M
+        return self.M * self.nbits // 8
 
     def codebook(self):
         return _pq_codebook(self)
 
     @property
     def codes(self):
-        """uint8 [ntotal * M] (faiss.vector_to_array(index.codes))."""
+        """uint8 [ntotal * code_size] (faiss.vector_to_array(index.codes))."""
         return self._codes(0, self.ntotal).reshape(-1)
 
     # ----------------------------------------------------------- build path
@@ -714,7 +716,7 @@ class IndexPQ(_HandleIndex):
         self._codebook_cache = None
 
     def set_trained(self, codebook):
-        """Install a trained codebook [M][256][d/M]."""
+        """Install a trained codebook [M][2^nbits][d/M]."""
         cb = np.ascontiguousarray(codebook, np.float32).reshape(-1)
         if cb.size != self.M * (1 << self.nbits) * (self.d // self.M):
             raise RuntimeError("codebook has the wrong size")
@@ -722,8 +724,8 @@ class IndexPQ(_HandleIndex):
         self._codebook_cache = None
 
     def add_codes(self, codes):
-        """Append precomputed codes uint8 [n][M]."""
-        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.M)
+        """Append precomputed codes uint8 [n][code_size]."""
+        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.code_size)
         _lib.check(self._c.add_codes(self._h, codes.shape[0], _ptr(codes)))
 
     def reconstruct_n(self, i0, n):
@@ -990,9 +992,14 @@ class IndexBinaryFlat(_HandleIndex):
 
 
 def decode_pq(codebook, codes):
-    """ProductQuantizer::decode: codebook [M][256][dsub], codes uint8 [n][M] -> float32 [n][M * dsub]."""
-    M, _, dsub = codebook.shape
-    codes = np.asarray(codes, np.uint8).reshape(-1, M)
+    """ProductQuantizer::decode: codebook [M][ksub][dsub], codes uint8 [n][code_size] -> float32 [n][M * dsub].
+    ksub = 256: a byte per sub-quantizer; ksub = 16: sub-quantizer 2i is the low nibble of byte i, 2i + 1 the high."""
+    M, ksub, dsub = codebook.shape
+    codes = np.asarray(codes, np.uint8)
+    if ksub == 16:
+        codes = codes.reshape(-1, M // 2)
+        codes = np.stack([codes & 15, codes >> 4], axis=2)
+    codes = codes.reshape(-1, M)
     out = np.empty((codes.shape[0], M * dsub), np.float32)
     for m in range(M):
         out[:, m * dsub:(m + 1) * dsub] = codebook[m][codes[:, m]]
@@ -1035,7 +1042,7 @@ def parse_factory(key):
     m = _FACTORY_RE.match(key.replace(" ", ""))
     if not m:
         raise RuntimeError(f"index_factory: unsupported key {key!r} "
-                           "(supported: '[OPQ<M>[_<dout>],]IVF<nlist>,PQ<M>[x8]', '[OPQ<M>[_<dout>],]PQ<M>[x8]', "
+                           "(supported: '[OPQ<M>[_<dout>],]IVF<nlist>,PQ<M>[x8]', '[OPQ<M>[_<dout>],]PQ<M>[x8|x4]', "
                            "'IVF<nlist>,Flat', 'IVF<nlist>,SQ8', 'IVF<nlist>,SQfp16', 'SQ8', 'SQfp16', 'Flat', each also behind a 'PCA[W][R]<dout>,' front)")
     nbits = int(m.group(5)) if m.group(5) else 8
     base = (int(m.group(3)), int(m.group(4)), nbits)
@@ -1045,7 +1052,7 @@ def parse_factory(key):
 
 
 def parse_pq_factory(key):
-    """'[OPQ<M>[_<dout>],]PQ<M>[x8]' -> (M, nbits) or (M, nbits, opq_M, opq_dout)
+    """'[OPQ<M>[_<dout>],]PQ<M>[x8|x4]' -> (M, nbits) or (M, nbits, opq_M, opq_dout)
     (opq_dout = -1: d); None for any other key."""
     m = _PQ_FACTORY_RE.match(key.replace(" ", ""))
     if not m:
@@ -1115,7 +1122,8 @@ def index_binary_factory(d, key, device=None):
 def index_factory(d, key, metric=METRIC_L2, device=None):
     """faiss.index_factory(d, "IVF1024,PQ16") (bench_polysemous_1bn.py:272), the
     OPQ-fronted "OPQ16,IVF262144,PQ16" (bench_gpu_1bn.py:10-17), the flat
-    "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224) and
+    "PQ96" / "OPQ96_384,PQ96" (the indexes of beir faiss_search.py:168-224), their 4-bit
+    forms "PQ32x4" / "OPQ32,PQ32x4" (nbits_experiments_fix_bytes_per_vec.py) and
     "IVF<nlist>,Flat" (bench_on_disk_performance.py:37; the "IVF1,Flat" ground
     truth of compute_ground_truth.py:311), "IVF<nlist>,SQ8" / "IVF<nlist>,SQfp16" (an
     IndexIVFScalarQuantizer, by_residual as in Faiss), the flat scalar quantizers "SQ8" / "SQfp16", and

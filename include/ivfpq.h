@@ -690,6 +690,13 @@ int ivfpq_host_get_pass_rows(int64_t n, int64_t in_bytes, int64_t* rows);
  * nloc of the nlist lists: the keys, the M * 2^nbits table entries and the buckets of a query
  * within 256 MiB, its nprobe * k * 64 bytes of partial lists within 2 GiB. */
 int ivfpq_get_query_chunk(int64_t nq, int nlist, int M, int nbits, int nloc, int nprobe, int k, int64_t* query_chunk);
+/* IndexPQ's search of nq queries over nb codes at nbits = 8 or 4: query_chunk = the queries per
+ * chunk (the [chunk][M][2^nbits] float tables within 256 MiB, at most 4096), and for a chunk of
+ * min(nq, query_chunk) queries G = queries per scan workgroup, ranges x rows = the code ranges (rows a
+ * multiple of 2048), S = 4 * ranges = the sorted partial lists per query.  Unsupported (M, nbits) or k
+ * is an error.  Null outputs are skipped. */
+int ivfpq_pq_get_plan(int M, int nbits, int k, int64_t nq, int64_t nb, int* G, int* ranges, int64_t* rows, int* S,
+                      int64_t* query_chunk);
 /* The queries per chunk of ivfpq_flat_search over nb rows. */
 int ivfpq_flat_search_get_query_chunk(int64_t n, int64_t nb, int64_t* query_chunk);
 /* The rows per pass of a k-means assignment to k centroids (every *_train). */
